@@ -2,7 +2,12 @@
 """Benchmark: env-steps/sec (whole node) of the batched cached-THOR VectorEnv.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--scenes 20]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints one JSON line. --full adds the
+CPU baseline, the rocprofv3 PMC passes and the A2C training legs to that line.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
 
 One bench step = one batched VectorEnv.step over all local envs: vn_step (transition,
 reward/done masking, auto-reset, gather of the image frame and goal frame into the output
@@ -50,6 +55,12 @@ def parse():
     p.add_argument("--warmup", type=int, default=500)
     p.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     p.add_argument("--scenes", type=int, default=20)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: the CPU baseline, the rocprofv3 PMC "
+                        "passes and the training legs (each still has its own --no-* switch)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed VectorEnv.step returned to DIR/<name>.npy "
+                        "(rank 0; the frames of a fixed, seeded sample of envs, the scalars of every env)")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--train-steps", type=int, default=6, help="timed A2C updates (0 = skip the train leg)")
@@ -620,6 +631,35 @@ def cpu_baseline(scenes, seconds, sweep="1,16,all"):
 
 
 # ---------------------------------------------------------------- GPU bench
+DUMP_SAMPLE_ENVS = 256  # envs whose frames --dump-outputs keeps (float32: 85 KB per frame)
+
+
+def dump_outputs(path, ret):
+    """--dump-outputs: what the last timed VectorEnv.step returned, one DIR/<name>.npy per
+    array. image / goal hold the frames of DUMP_SAMPLE_ENVS envs drawn once with a fixed seed
+    (all of them when there are no more; 4096 envs x 2 frames would be 694 MB as float32),
+    sample_envs their indices; reward, done, state and the other info arrays hold every env.
+    Integers and booleans are stored exactly (u8 frames as float32, the rest as float64)."""
+    (image, goal), reward, done, info = ret
+    E = image.shape[0]
+    if E > DUMP_SAMPLE_ENVS:
+        pick = np.sort(np.random.default_rng(0).choice(E, DUMP_SAMPLE_ENVS, replace=False))
+    else:
+        pick = np.arange(E)
+    idx = torch.as_tensor(pick, device=image.device)
+    arrays = {"image": image[idx].cpu().numpy().astype(np.float32),
+              "goal": goal[idx].cpu().numpy().astype(np.float32),
+              "sample_envs": pick.astype(np.float64),
+              "reward": reward.cpu().numpy().astype(np.float32),
+              "done": done.cpu().numpy().astype(np.float64)}
+    for k, v in info.items():
+        if isinstance(v, torch.Tensor):
+            arrays[k] = v.cpu().numpy().astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -633,12 +673,15 @@ def main():
         torch.cuda.set_device(0)
         run_leg(args.pmc_leg, args, scenes, torch.device("cuda", 0), 1, 0, updates=1, warmup=1, marker=True)
         return
+    # a plain run does only what the headline figure needs: set up, warm up, the timed steps.
+    # The CPU baseline, the PMC passes and the training legs run under --full
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(scenes, args.cpu_seconds, args.cpu_sweep)
     traffic, traffic_info = None, None
     mfma_pmc = {}
-    if rank == 0 and world == 1 and not args.no_pmc:  # child rocprofv3 runs, before this process touches the GPU
+    # child rocprofv3 runs, before this process touches the GPU
+    if rank == 0 and world == 1 and args.full and not args.no_pmc:
         traffic, traffic_info = pmc_traffic(args.envs, args.scenes)
         if args.train_steps > 0:
             for leg in ("84", "174", "c5"):
@@ -691,8 +734,9 @@ def main():
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     ev0.record()
+    last = None
     for k in range(K):
-        env.step(step_actions[step], out=out)
+        last = env.step(step_actions[step], out=out)
         step += 1
     ev1.record()
     # poll the end event before the synchronize: a blocking wait that outlasts the runtime's
@@ -709,9 +753,11 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed, kern_ms = float(t[0]), float(t[1])
     flags = env.error_flags()
-    del env, out
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, last)
+    del env, out, last
     legs = {}
-    if args.train_steps > 0:
+    if args.full and args.train_steps > 0:
         torch.cuda.empty_cache()
         for leg in LEG_ORDER:
             if not leg_enabled(args, leg, world):

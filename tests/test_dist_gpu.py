@@ -207,7 +207,7 @@ def test_bench_world2_line_carries_dist_record(tmp_path):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "20",
-           "--warmup", "5", "--envs", "64", "--scenes", "2", "--train-steps", "2", "--train-warmup", "1",
+           "--warmup", "5", "--envs", "64", "--scenes", "2", "--full", "--train-steps", "2", "--train-warmup", "1",
            "--no-train-ref", "--no-c5", "--dist-backend", "gloo", "--allreduce-buckets", "2"]
     r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-4000:]

@@ -11,7 +11,7 @@ for rep in 1 2; do
     d=$ROOT/gpurun_out/fab_${v}_$rep
     if [ $v = on ]; then export $FLAG=1; else unset $FLAG; fi
     (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $d -o run \
-       -- python3 $ROOT/bench.py ${BENCH_BASE:---no-c5} --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --train-steps 2 \
+       -- python3 $ROOT/bench.py --full ${BENCH_BASE:---no-c5} --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --train-steps 2 \
        --train-warmup 1 ${LEG_ARGS:---no-train-ff --no-train-ref4} > $d.log 2>&1) || exit 1
     echo "$FLAG=$v rep $rep: $(grep -o '"ms_per_update": [0-9.]*' $d.log | tr '\n' ' ')"
     python3 - $d/run_kernel_trace.csv <<'PY'

@@ -9,7 +9,7 @@ timeout -k 10 500 python -u -m pytest tests/test_replay_gpu.py -x -q --timeout 3
 for rep in 1 2 3; do
   for v in side main; do
     if [ $v = main ]; then export VN_AUX_REPLAY_MAIN=1; else unset VN_AUX_REPLAY_MAIN; fi
-    timeout -k 10 300 python3 bench.py --no-c5 --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --no-train-84 \
+    timeout -k 10 300 python3 bench.py --full --no-c5 --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --no-train-84 \
       --no-train-ff --no-train-174 --no-short --train-steps 1 --train-warmup 0 > gpurun_out/r6s_$v.log 2>&1 || exit 1
     python3 - gpurun_out/r6s_$v.log $v $rep <<'PY'
 import json, sys

@@ -11,7 +11,7 @@ cp $L /tmp/new.so
 for rep in $(seq ${REPS:-3}); do
   for v in new $ALT; do
     if [ $v = new ]; then cp /tmp/new.so $L; else cp tools/ab/$v $L; fi
-    timeout -k 10 300 python3 bench.py --no-c5 --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --no-train-ff \
+    timeout -k 10 300 python3 bench.py --full --no-c5 --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --no-train-ff \
       --no-train-84 --no-train-174 --no-short > gpurun_out/r4ab_${v}_$rep.log 2>&1 || { cp /tmp/new.so $L; exit 1; }
     python3 - gpurun_out/r4ab_${v}_$rep.log $v $rep <<'PY'
 import json, sys

@@ -8,7 +8,7 @@ cd $ROOT
 for rep in $(seq 1 ${REPS:-3}); do
   for v in merged separate; do
     if [ $v = merged ]; then export VN_REPLAY_MERGED=1; else unset VN_REPLAY_MERGED; fi
-    timeout -k 10 300 python3 bench.py --no-c5 --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --no-train-84 \
+    timeout -k 10 300 python3 bench.py --full --no-c5 --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --no-train-84 \
       --no-train-ff --no-train-174 --no-short --train-steps 1 --train-warmup 0 > gpurun_out/replay_ab_$v.log 2>&1 || exit 1
     python3 - gpurun_out/replay_ab_$v.log $v $rep <<'PY'
 import json, sys

@@ -17,7 +17,7 @@ done
 ARGS="--no-cpu-baseline --no-pmc --no-train-ff --no-train-84 --no-train-174 --no-c5 --no-short"
 for rep in 1 2; do
   for r in ${BRS:-4 2 8}; do
-    VN_C34_ROWS=$r timeout -k 10 300 python bench.py $ARGS > $OUT/bench_$r.$rep.log 2>&1 || exit 1
+    VN_C34_ROWS=$r timeout -k 10 300 python bench.py --full $ARGS > $OUT/bench_$r.$rep.log 2>&1 || exit 1
     python3 -c "
 import json
 d=json.loads([l for l in open('$OUT/bench_$r.$rep.log') if l.startswith('{')][-1])

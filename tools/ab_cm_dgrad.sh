@@ -14,7 +14,7 @@ ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-pmc --no-train-ff --no-train-
 for rep in 1 2; do
   for cfg in 64 128; do
     if [ $cfg = 128 ]; then E="VN_CM_DGRAD_128=1"; else E=""; fi
-    env $E timeout -k 10 400 python bench.py $ARGS > $OUT/bench_$cfg.$rep.log 2>&1 || exit 1
+    env $E timeout -k 10 400 python bench.py --full $ARGS > $OUT/bench_$cfg.$rep.log 2>&1 || exit 1
     python3 -c "
 import json
 d=json.loads([l for l in open('$OUT/bench_$cfg.$rep.log') if l.startswith('{')][-1])

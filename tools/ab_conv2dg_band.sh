@@ -18,9 +18,9 @@ ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-pmc --no-train-ff --no-train-
 for rep in 1 2; do
   for by in 0 8 14; do
     if [ $by = 0 ]; then
-      timeout -k 10 300 python bench.py $ARGS > $OUT/bench_$by.$rep.log 2>&1 || exit 1
+      timeout -k 10 300 python bench.py --full $ARGS > $OUT/bench_$by.$rep.log 2>&1 || exit 1
     else
-      VN_CONV2DG_BAND=$by timeout -k 10 300 python bench.py $ARGS > $OUT/bench_$by.$rep.log 2>&1 || exit 1
+      VN_CONV2DG_BAND=$by timeout -k 10 300 python bench.py --full $ARGS > $OUT/bench_$by.$rep.log 2>&1 || exit 1
     fi
     python3 -c "
 import json,sys

@@ -11,7 +11,7 @@ OUT=$ROOT/gpurun_out/ab_conv3
 mkdir -p $OUT
 for cfg in ${CFGS:-0 1 2 3 4}; do
   cd /tmp && VN_C3_CFG=$cfg timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/p$cfg -o run \
-    -- python3 $ROOT/bench.py --no-c5 --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --train-steps 2 --train-warmup 1 \
+    -- python3 $ROOT/bench.py --full --no-c5 --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --train-steps 2 --train-warmup 1 \
     --no-train-ff --no-train-ref4 > $OUT/cfg$cfg.log 2>&1 || exit 1
   S=$(find $OUT/p$cfg -name '*kernel_stats.csv' | head -1)
   echo "== cfg $cfg"

@@ -13,7 +13,7 @@ for rep in 1 2; do
     case $cfg in
       none) E="" ;; dx1) E="VN_NT_DX1=1" ;; x1) E="VN_NT_X1=1" ;; both) E="VN_NT_DX1=1 VN_NT_X1=1" ;;
     esac
-    env $E timeout -k 10 300 python bench.py $ARGS > $OUT/bench_$cfg.$rep.log 2>&1 || exit 1
+    env $E timeout -k 10 300 python bench.py --full $ARGS > $OUT/bench_$cfg.$rep.log 2>&1 || exit 1
     python3 -c "
 import json
 d=json.loads([l for l in open('$OUT/bench_$cfg.$rep.log') if l.startswith('{')][-1])

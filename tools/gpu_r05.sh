@@ -25,13 +25,13 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
   echo "== bench ${BENCH_ARGS:-}"
-  timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > $OUT/bench_$TAG.log 2>&1
+  timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench_$TAG.log 2>&1
   rc=$?; tail -1 $OUT/bench_$TAG.log | cut -c1-400; [ $rc -eq 0 ] || exit $rc
 fi
 if [ -n "${LEG_ARGS:-}" ]; then
   echo "== rocprofv3 $LEG_ARGS"
   cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/prof_$TAG -o run \
-    -- python3 $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pmc $LEG_ARGS > $ROOT/$OUT/prof_$TAG.log 2>&1
+    -- python3 $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-pmc $LEG_ARGS > $ROOT/$OUT/prof_$TAG.log 2>&1
   rc=$?; cd $ROOT; [ $rc -eq 0 ] || exit $rc
 fi
 echo "== done"

@@ -10,7 +10,7 @@ timeout -k 10 400 python -u -m pytest -q --timeout 240 --timeout-method thread \
 rc=$?; tail -2 gpurun_out/pytest_ab_conv2f.log; [ $rc -eq 0 ] || exit $rc
 for v in 0 1 0 1; do
   if [ $v = 0 ]; then export VN_CONV2F_GENERIC=1; else unset VN_CONV2F_GENERIC; fi
-  timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pmc --no-train-84 --no-train-ff \
+  timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-pmc --no-train-84 --no-train-ff \
     --no-train-ref --train-steps 3 > gpurun_out/ab_conv2f_$v.log 2>&1 || exit $?
   echo "band=$v $(grep -o '"train_c5_300x400": {[^}]*' gpurun_out/ab_conv2f_$v.log | grep -o '"ms_per_update": [0-9.]*')"
 done
