@@ -61,6 +61,34 @@ __global__ void returns_kernel(const float* __restrict__ rewards, const uint8_t*
   }
 }
 
+// softmax_stats (vn_common.h) for the loss: the same sums in the same order, but once the
+// other actions' mass so = sum_{j != argmax} exp(lg_j - mx) is below 2^-6 the log of the sum is
+// log1pf(so) instead of logf(1 + so). logf(s) carries the absolute error 2^-24 of rounding
+// s = 1 + so whatever the size of ls, so the dominant action's log-probability -ls, and with
+// it the entropy of a saturated distribution, lost their relative precision as s -> 1 (from
+// so < 2^-24 on they were exactly 0). At so >= 2^-6 logf(s) is within 2^-24 (1 + so) / ls <
+// 4e-6 of ls and is kept: every unsaturated sample computes the bits it computed before.
+__device__ __forceinline__ void softmax_stats_loss(const float* lg, int A, float* p, float* logp, float& H) {
+  float mx = lg[0];
+  for (int j = 1; j < A; ++j) mx = fmaxf(mx, lg[j]);
+  int jm = 0;
+  for (int j = A - 1; j >= 0; --j)
+    if (lg[j] == mx) jm = j;
+  float s = 0.0f, so = 0.0f;
+  for (int j = 0; j < A; ++j) {
+    const float e = expf(lg[j] - mx);
+    s += e;
+    if (j != jm) so += e;
+  }
+  const float ls = so < 0.015625f ? log1pf(so) : logf(s);
+  H = 0.0f;
+  for (int j = 0; j < A; ++j) {
+    logp[j] = lg[j] - mx - ls;
+    p[j] = expf(logp[j]);
+    H -= p[j] * logp[j];
+  }
+}
+
 // dL/d(head outputs) for L = vc mean(A^2) - mean(A logp_a) - ec mean(H); stats += block sums of
 // (A^2, -A logp_a, H, R).
 __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict__ out, const int32_t* __restrict__ actions,
@@ -71,7 +99,7 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict_
   if (i < n) {
     float lg[7], p[7], lp[7], H;
     for (int j = 0; j < A; ++j) lg[j] = out[(int64_t)i * OUT_LD_A2C + j];
-    softmax_stats(lg, A, p, lp, H);
+    softmax_stats_loss(lg, A, p, lp, H);
     const int a = actions[i];
     const float R = returns[i];
     const float V = out[(int64_t)i * OUT_LD_A2C + A];

@@ -458,6 +458,8 @@ int vn_goal_runs_rollout(const uint8_t* dones, int T, int E, int32_t* list, int3
 /* ---- A2C (the deep_rl trainer contract; DESIGN.md "A2C contract") ---- */
 int vn_policy_sample(const float* out, int n, int num_actions, uint64_t seed, uint64_t counter,
                      int32_t* actions, float* logp, float* entropy, float* value, vn_stream_t stream);
+/* actions[i] = argmax over logits 0..A-1 of out [n][8]; on an exact tie the first (lowest)
+ * maximal index wins, as numpy / torch argmax. Columns >= A are not read. */
 int vn_policy_greedy(const float* out, int n, int num_actions, int32_t* actions, vn_stream_t stream);
 int vn_a2c_returns(const float* rewards, const uint8_t* dones, const float* bootstrap_out, int T, int E,
                    int num_actions, float gamma, float* returns, vn_stream_t stream);

@@ -17,5 +17,8 @@ Modules
   envs.py     cached.py env (single), the batched VectorEnv contract, maze env
   frames.py   synthetic frame hash (scene, state, word) -> uint8 frames
   policy.py   BigGoalHouseModel trunk + heads in torch fp32 (CPU)
-  a2c.py      n-step returns / A2C loss / clip / RMSprop restated in torch fp32 (CPU)
+  a2c.py      n-step returns / A2C loss / clip / RMSprop restated in torch fp32 (CPU), and
+              the float64 numpy references of the A2C step / update kernels (*64)
+  a2c_cases.py  deterministic inputs of the A2C step tests (shared by the GPU tests and
+              the CPU check of their draws' distance to the CDF boundaries)
 """
