@@ -182,8 +182,22 @@ __global__ __launch_bounds__(kRpThreads) void unreal_rp_loss_kernel(const float*
     const float ex[3] = {expf(l[0] - m), expf(l[1] - m), expf(l[2] - m)};
     const float z = ex[0] + ex[1] + ex[2];
     float* g = dlogits + (int64_t)j * 4;
+    // p_cls - 1 = -(the other classes' mass) / z: once that mass is below 2^-6 z the difference
+    // is taken in this form. ex[cls] / z - 1 carries the absolute error 2^-24 of rounding the
+    // quotient next to 1, so a trained predictor's class gradient lost its relative precision
+    // (from a margin of about 18 on it was exactly 0 while the other two classes kept theirs). Above
+    // the threshold the difference is within 2^-24 / 2^-6 < 4e-6 of itself and is kept: every
+    // unsaturated sample computes the bits it computed before.
+    float oth = 0.0f;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) g[c] = used ? (ex[c] / z - (c == cls ? 1.0f : 0.0f)) * weight * inv : 0.0f;
+    for (int c = 0; c < 3; ++c)
+      if (c != cls) oth += ex[c];
+    const bool sat = oth < 0.015625f * z;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float pd = c == cls ? (sat ? -oth / z : ex[c] / z - 1.0f) : ex[c] / z;
+      g[c] = used ? pd * weight * inv : 0.0f;
+    }
     g[3] = 0.0f;
     if (used) ce += logf(z) + m - l[cls];
   }

@@ -183,6 +183,84 @@ def test_aux_loss_kernel_vs_oracle():
     _close(stats[:3].cpu().numpy() / numel, np.array([x.item() for x in losses]), 1e-5, "per-head MSE")
 
 
+def _random_aux_arena(rows, hw, seed):
+    rng = np.random.RandomState(seed)
+    return (rng.randint(0, 256, size=(rows,) + hw + (1,)).astype(np.uint8),
+            rng.randint(0, 256, size=(rows,) + hw + (3,)).astype(np.uint8))
+
+
+@pytest.mark.parametrize("hw,margins", [((84, 84), (6, 6)), ((174, 174), (3, 3)), ((300, 400), (2, 4))])
+def test_aux_target_table_vs_fp64(hw, margins):
+    """aux_target_table_kernel on random u8 frames against the float64 centre crop + 4x4 mean of
+    u8 / 255 (crop margins 6/6, 3/3, and 2/4 with a non-square map). rtol 1e-6: the kernel's
+    value is an exact integer sum (<= 16 * 255) times one rounded constant. Frames smaller than
+    the crop are refused."""
+    from oracle.unreal_cases import aux_table_ref
+    from vnav import _lib
+    from vnav.policy import PolicyNet
+    net = PolicyNet(hw, 4, aux=True)
+    ph, pw = net.aux_layout["p_hw"]
+    assert ((hw[0] - 4 * ph) // 2, (hw[1] - 4 * pw) // 2) == margins
+    depth, seg = _random_aux_arena(3, hw, 11)
+    table = net.aux_target_table(torch.as_tensor(depth).cuda(), torch.as_tensor(seg).cuda())
+    torch.cuda.synchronize()
+    want = aux_table_ref(depth, seg, ph, pw)
+    got = table.cpu().numpy().astype(np.float64)
+    err = (np.abs(got - want) / np.maximum(np.abs(want), 1e-300)).max()
+    print("FIGURE aux table %dx%d: %.3g / 1e-06" % (hw[0], hw[1], err))
+    np.testing.assert_allclose(got, want, rtol=1e-6, atol=0.0)
+    assert want.min() > 0.0 and len(np.unique(want)) > 1000
+    small = torch.zeros((1, 4 * ph - 1, hw[1], 3), dtype=torch.uint8, device="cuda")
+    sentinel = table.clone()
+    rc = net.lib.vn_aux_target_table(net._h, _lib.ptr(small), _lib.ptr(small), 4 * ph - 1, hw[1], 1, _lib.ptr(table), None)
+    torch.cuda.synchronize()
+    assert rc != 0 and torch.equal(table, sentinel)
+
+
+@pytest.mark.parametrize("n", [297, 300])
+def test_aux_loss_kernel_grid_stride_vs_fp64(n):
+    """aux_loss_grad_kernel at 174x174 (42x42 map) below and above its 2048 x 256 lanes: 297
+    samples are 523908 items, 300 are 529200, so the grid-stride loop runs a second time for the
+    last 4912. A 5-row table, img_rows != goal_rows on nine samples in ten, stats prefilled.
+    The reference is the float64 MSE against the float64 targets."""
+    from oracle.unreal_cases import aux_table_ref
+    from vnav.policy import AuxTargets, PolicyNet
+    hw, rows, w, prefill = (174, 174), 5, 0.05, 0.25
+    net = PolicyNet(hw, 4, aux=True)
+    ph, pw = net.aux_layout["p_hw"]
+    assert (ph, pw) == (42, 42) and (n * ph * pw > 2048 * 256) == (n == 300)
+    depth, seg = _random_aux_arena(rows, hw, 12)
+    rng = np.random.RandomState(n)
+    ri = rng.randint(0, rows, size=n).astype(np.int32)
+    rg = ((ri + 1 + rng.randint(0, rows - 1, size=n)) % rows).astype(np.int32)
+    rg[::10] = ri[::10]
+    assert (ri != rg).mean() > 0.8 and (ri == rg).any() and set(ri.tolist()) == set(range(rows))
+    pred = rng.rand(n, ph, pw, 8).astype(np.float32)
+    table = net.aux_target_table(torch.as_tensor(depth).cuda(), torch.as_tensor(seg).cuda())
+    rows_i, rows_g = torch.as_tensor(ri).cuda(), torch.as_tensor(rg).cuda()
+    tg = AuxTargets(table.data_ptr(), rows_i.data_ptr(), rows_g.data_ptr())
+    dpred = torch.full((n + 1, ph, pw, 8), 5.0, device="cuda")  # one guard sample
+    stats = torch.full((4,), prefill, device="cuda")
+    dp = torch.as_tensor(pred).cuda()
+    net.aux_loss_grad(dp, n, tg, w, dpred, stats)
+    torch.cuda.synchronize()
+    t = aux_table_ref(depth, seg, ph, pw)
+    target = np.concatenate((t[ri], t[rg][..., 1:]), axis=-1)  # depth, seg, the goal's seg
+    diff = pred[..., :7].astype(np.float64) - target
+    numel = np.array([1, 3, 3, 3, 3, 3, 3], dtype=np.float64) * n * ph * pw
+    want = 2.0 * float(np.float32(w)) * diff / numel
+    got = dpred.cpu().numpy()
+    print("FIGURE aux dpred n=%d: %.3g / 1e-05" % (n, np.abs(got[:n, ..., :7] - want).max() / np.abs(want).max()))
+    _close(got[:n, ..., :7], want, 1e-5, "dpred")
+    assert not got[:n, ..., 7].any() and (got[n] == 5.0).all()
+    sums = np.array([(diff[..., 0:1] ** 2).sum(), (diff[..., 1:4] ** 2).sum(), (diff[..., 4:7] ** 2).sum()])
+    st = stats.cpu().numpy().astype(np.float64)
+    print("FIGURE aux sums n=%d: %s / 1e-05" % (n, np.abs(st[:3] - prefill - sums) / sums))
+    np.testing.assert_allclose(st[:3] - prefill, sums, rtol=1e-5)
+    assert st[3] == prefill
+    assert torch.equal(dp.cpu(), torch.as_tensor(pred))
+
+
 @pytest.mark.parametrize("hw", [(84, 84), (174, 174)])
 def test_fused_aux_forward_loss_matches_unfused(hw):
     """The trainer's fused path (second head layer as a direct kernel computing each
