@@ -13,7 +13,8 @@
 // The per-env state is wave-uniform (scalar loads); a reset runs 64 Philox start
 // candidates in parallel, one per lane, and a wave ballot picks the first valid one —
 // the same result as the sequential rejection loop over the same counter stream.
-// The two frames are then streamed with 16-B lanes, 8 loads in flight per lane.
+// The two frames are then streamed with 16-B lanes, 8 loads in flight per lane; with output
+// reuse on (vn_set_output_reuse) a frame whose output row already holds it is not copied.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -103,6 +104,11 @@ struct EnvArgs {
   const float* head_b;
   const float* head_x;
   float* head_out;
+  // output reuse (DESIGN.md "vn_step: output reuse"): what each env last wrote, and whether
+  // this launch may skip a frame whose destination row already holds it
+  uint64_t* rec_addr;  // [2][n_envs] destination address of the last image / goal row written
+  int32_t* rec_row;    // [2][n_envs] arena row whose bytes went there
+  int reuse;
 };
 
 // MODE_STEP_HEADS: a step of vn_step_a2c that also computes the policy heads (its own
@@ -236,6 +242,47 @@ __device__ __forceinline__ void copy_two_frames(uint8_t* __restrict__ d1, const 
   }
 }
 
+// Copy one frame (the other one of the env is already in its output row): the same 8 x 16 B
+// in flight per lane as copy_two_frames, on one stream. The trip count is wave-uniform; the
+// remainder (1323 uint4 per 84x84x3 frame = 2 trips of 512 + 299) issues all its predicated
+// loads before its stores.
+template <int VEC>
+__device__ __forceinline__ void copy_one_frame(uint8_t* __restrict__ d, const uint8_t* __restrict__ s,
+                                               int64_t bytes, int lane) {
+  if constexpr (VEC == 16) {
+    constexpr int U = 8;
+    const int n = (int)(bytes >> 4);
+    const uint4* a = reinterpret_cast<const uint4*>(s);
+    uint4* x = reinterpret_cast<uint4*>(d);
+    int base = 0;
+    for (; base + 64 * U <= n; base += 64 * U) {
+      const int i = base + lane;
+      uint4 v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[u] = a[i + 64 * u];
+#pragma unroll
+      for (int u = 0; u < U; ++u) st16_nt(x + i + 64 * u, v[u]);
+    }
+    if (base < n) {
+      const int i = base + lane;
+      uint4 v[U] = {};
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (i + 64 * u < n) v[u] = a[i + 64 * u];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (i + 64 * u < n) st16_nt(x + i + 64 * u, v[u]);
+    }
+  } else if constexpr (VEC == 4) {
+    const int n = (int)(bytes >> 2);
+    const uint32_t* a = reinterpret_cast<const uint32_t*>(s);
+    uint32_t* x = reinterpret_cast<uint32_t*>(d);
+    for (int i = lane; i < n; i += 64) x[i] = a[i];
+  } else {
+    for (int64_t i = lane; i < bytes; i += 64) d[i] = s[i];
+  }
+}
+
 template <int MODE, int VEC>
 __global__ __launch_bounds__(256) void env_kernel(EnvArgs a) {
   const int lane = threadIdx.x & 63;
@@ -248,6 +295,16 @@ __global__ __launch_bounds__(256) void env_kernel(EnvArgs a) {
   int s = st[ST_STATE * n_envs + e];
   int g = st[ST_GOAL * n_envs + e];
   int os = st[ST_OBS * n_envs + e];
+  // this env's output record, loaded with the state (wave-uniform, before any store of the
+  // kernel); only a launch that may skip frames reads it
+  uint64_t rec_a1 = 0, rec_a2 = 0;
+  int32_t rec_r1 = -1, rec_r2 = -1;
+  if (MODE != MODE_STEP_HEADS && a.reuse) {
+    rec_a1 = a.rec_addr[e];
+    rec_a2 = a.rec_addr[n_envs + e];
+    rec_r1 = a.rec_row[e];
+    rec_r2 = a.rec_row[n_envs + e];
+  }
 
   if constexpr (MODE == MODE_STEP || MODE == MODE_STEP_HEADS) {
     int t = st[ST_ELAPSED * n_envs + e];
@@ -384,15 +441,39 @@ __global__ __launch_bounds__(256) void env_kernel(EnvArgs a) {
     if (a.info_img_row) a.info_img_row[e] = (int32_t)img_row;
     if (a.info_goal_row) a.info_goal_row[e] = (int32_t)goal_row;
   }
+  if constexpr (MODE == MODE_STEP_HEADS) return;  // vn_step_a2c is index-only: no frame tail
   if (a.obs != nullptr && a.goal_out != nullptr) {
     const int64_t F = a.frame_bytes;
-    copy_two_frames<VEC>(a.obs + (int64_t)e * F, a.arena + img_row * F, a.goal_out + (int64_t)e * F,
-                         a.arena + goal_row * F, F, lane);
+    uint8_t* d1 = a.obs + (int64_t)e * F;
+    uint8_t* d2 = a.goal_out + (int64_t)e * F;
+    // a frame is skipped when this env's last write to the same row put the same arena row
+    // there (the caller leaves the rows alone in between: vn_set_output_reuse's contract)
+    const bool keep1 = a.reuse && rec_a1 == (uint64_t)d1 && rec_r1 == (int32_t)img_row;
+    const bool keep2 = a.reuse && rec_a2 == (uint64_t)d2 && rec_r2 == (int32_t)goal_row;
+    if (!keep1 && !keep2)
+      copy_two_frames<VEC>(d1, a.arena + img_row * F, d2, a.arena + goal_row * F, F, lane);
+    else if (!keep1)
+      copy_one_frame<VEC>(d1, a.arena + img_row * F, F, lane);
+    else if (!keep2)
+      copy_one_frame<VEC>(d2, a.arena + goal_row * F, F, lane);
+    if (lane == 0) {
+      a.rec_addr[e] = (uint64_t)d1;
+      a.rec_addr[n_envs + e] = (uint64_t)d2;
+      a.rec_row[e] = (int32_t)img_row;
+      a.rec_row[n_envs + e] = (int32_t)goal_row;
+    }
   } else if (a.obs != nullptr || a.goal_out != nullptr) {
     const int64_t F = a.frame_bytes;
-    uint8_t* d = a.obs ? a.obs + (int64_t)e * F : a.goal_out + (int64_t)e * F;
-    const uint8_t* src = a.arena + (a.obs ? img_row : goal_row) * F;
+    const int k = a.obs ? 0 : 1;  // which frame: always copied, its record updated
+    uint8_t* d = (k == 0 ? a.obs : a.goal_out) + (int64_t)e * F;
+    const uint8_t* src = a.arena + (k == 0 ? img_row : goal_row) * F;
     for (int64_t i = lane; i < F; i += 64) d[i] = src[i];
+    if (lane == 0) {
+      a.rec_addr[k * n_envs + e] = (uint64_t)d;
+      a.rec_row[k * n_envs + e] = (int32_t)(k == 0 ? img_row : goal_row);
+      // the other frame's record no longer holds if this row was its destination
+      if (a.rec_addr[(1 - k) * n_envs + e] == (uint64_t)d) a.rec_addr[(1 - k) * n_envs + e] = 0;
+    }
   }
 }
 
@@ -467,6 +548,11 @@ struct vn_ctx {
   uint8_t* info_trunc = nullptr;
   int32_t* info_img_row = nullptr;
   int32_t* info_goal_row = nullptr;
+  // output reuse: the per-env records (device, stream-ordered) and the host switch
+  uint64_t* rec_addr = nullptr;
+  int32_t* rec_row = nullptr;
+  int reuse = 0;       // vn_set_output_reuse
+  int reuse_arm = 0;   // the next two-frame launch still writes every row
 };
 
 namespace {
@@ -512,7 +598,26 @@ EnvArgs make_args(vn_ctx* c) {
   a.info_trunc = c->info_trunc;
   a.info_img_row = c->info_img_row;
   a.info_goal_row = c->info_goal_row;
+  a.rec_addr = c->rec_addr;
+  a.rec_row = c->rec_row;
   return a;
+}
+
+// Whether a launch writing to (obs, goal) may skip rows that already hold their frame. The
+// first executed two-frame launch after vn_set_output_reuse(ctx, 1) consumes the armed full
+// write. A launch that is only being captured into a graph has not run yet (and may never):
+// while armed it is recorded as a full write and leaves the arm for the next eager launch.
+// A one-frame launch copies unconditionally and leaves the arm for the next two-frame one.
+int take_reuse(vn_ctx* c, const uint8_t* obs, const uint8_t* goal, hipStream_t stream) {
+  if (!obs || !goal || !c->reuse) return 0;
+  if (!c->reuse_arm) return 1;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &cap) != hipSuccess) {
+    (void)hipGetLastError();  // e.g. the legacy stream while another one captures: not a capture of ours
+    cap = hipStreamCaptureStatusNone;
+  }
+  if (cap == hipStreamCaptureStatusNone) c->reuse_arm = 0;
+  return 0;
 }
 
 template <int MODE>
@@ -534,7 +639,7 @@ int launch_env(vn_ctx* c, const EnvArgs& a, hipStream_t stream) {
 void free_ctx(vn_ctx* c) {
   if (!c) return;
   void* ptrs[] = {c->arena, c->graph, c->spd, c->scenes, c->st, c->ep_ret, c->env_scene,
-                  c->tasks, c->sched, c->flags, c->cur_order, c->cur_count};
+                  c->tasks, c->sched, c->flags, c->cur_order, c->cur_count, c->rec_addr, c->rec_row};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete c;
@@ -633,7 +738,8 @@ int vn_create(const vn_scene_desc* scenes, int n_scenes, int n_envs, uint64_t se
   bool ok = alloc((void**)&c->arena, (size_t)(rows * F)) && alloc((void**)&c->graph, g32.size() * 4) &&
             alloc((void**)&c->spd, spd32.size() * 4) && alloc((void**)&c->scenes, sh.size() * sizeof(SceneDev)) &&
             alloc((void**)&c->st, (size_t)ST_COUNT * n_envs * 4) && alloc((void**)&c->ep_ret, (size_t)n_envs * 4) &&
-            alloc((void**)&c->env_scene, (size_t)n_envs * 4) && alloc((void**)&c->flags, 4);
+            alloc((void**)&c->env_scene, (size_t)n_envs * 4) && alloc((void**)&c->flags, 4) &&
+            alloc((void**)&c->rec_addr, (size_t)2 * n_envs * 8) && alloc((void**)&c->rec_row, (size_t)2 * n_envs * 4);
   if (!ok) {
     free_ctx(c);
     return fail(VN_ENOMEM, "vn_create: device allocation failed");
@@ -648,6 +754,9 @@ int vn_create(const vn_scene_desc* scenes, int n_scenes, int n_envs, uint64_t se
   if (e == hipSuccess) e = hipMemset(c->st, 0, (size_t)ST_COUNT * n_envs * 4);
   if (e == hipSuccess) e = hipMemset(c->ep_ret, 0, (size_t)n_envs * 4);
   if (e == hipSuccess) e = hipMemset(c->flags, 0, 4);
+  // a null address matches no destination: the first launch writes every row
+  if (e == hipSuccess) e = hipMemset(c->rec_addr, 0, (size_t)2 * n_envs * 8);
+  if (e == hipSuccess) e = hipMemset(c->rec_row, 0, (size_t)2 * n_envs * 4);
   for (int k = 0; k < n_scenes && e == hipSuccess; ++k) {
     const vn_scene_desc& d = scenes[k];
     if (d.companion)
@@ -705,6 +814,7 @@ int vn_observe(vn_ctx* c, uint8_t* obs_dev, uint8_t* goal_dev, int32_t* state_de
   a.obs = obs_dev;
   a.goal_out = goal_dev;
   a.state_out = state_dev;
+  a.reuse = take_reuse(c, obs_dev, goal_dev, (hipStream_t)stream);
   return launch_env<MODE_OBSERVE>(c, a, (hipStream_t)stream);
 }
 
@@ -720,6 +830,7 @@ int vn_step(vn_ctx* c, const int32_t* actions_dev, uint8_t* obs_dev, uint8_t* go
   a.reward = reward_dev;
   a.done = done_dev;
   a.state_out = state_dev;
+  a.reuse = take_reuse(c, obs_dev, goal_dev, (hipStream_t)stream);
   return launch_env<MODE_STEP>(c, a, (hipStream_t)stream);
 }
 
@@ -896,6 +1007,13 @@ int vn_set_max_episode_steps(vn_ctx* c, int max_steps) {
 int vn_set_autoreset(vn_ctx* c, int on) {
   if (!c) return fail(VN_EINVAL, "vn_set_autoreset: NULL ctx");
   c->autoreset = on ? 1 : 0;
+  return VN_OK;
+}
+
+int vn_set_output_reuse(vn_ctx* c, int on) {
+  if (!c) return fail(VN_EINVAL, "vn_set_output_reuse: NULL ctx");
+  c->reuse = on ? 1 : 0;
+  c->reuse_arm = c->reuse;
   return VN_OK;
 }
 

@@ -108,6 +108,7 @@ SIGNATURES = {
     "vn_set_curriculum": (c_int, [c_void_p, c_double, c_int, c_double]),
     "vn_set_curriculum_scenes": (c_int, [c_void_p, c_double, c_void_p, c_void_p]),
     "vn_set_autoreset": (c_int, [c_void_p, c_int]),
+    "vn_set_output_reuse": (c_int, [c_void_p, c_int]),
     "vn_random_actions": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p]),
     "vn_get_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vn_set_state": (c_int, [c_void_p, c_void_p, c_void_p]),

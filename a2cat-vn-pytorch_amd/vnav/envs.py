@@ -31,7 +31,7 @@ class VectorEnv:
     num_actions = 4  # THORDiscreteCachedEnv.get_action_size (cached.py:66-68)
 
     def __init__(self, scenes, num_envs, seed=0, device=None, max_episode_steps=900, tasks=None,
-                 env_scenes=None, autoreset=True, aux_observations=False):
+                 env_scenes=None, autoreset=True, aux_observations=False, reuse_outputs=True):
         if isinstance(scenes, Scene):
             scenes = [scenes]
         if not scenes:
@@ -72,6 +72,10 @@ class VectorEnv:
         # recaptured (A2CTrainer checks it before each replay)
         self.config_generation = 0
         self._out_cache = None
+        # output reuse (vn_set_output_reuse): armed only while the caller
+        # steps into its own buffers; _reuse_on mirrors the native switch
+        self.reuse_outputs = bool(reuse_outputs)
+        self._reuse_on = False
         E = self.num_envs
         kw = dict(device=self.device)
         self._info = dict(
@@ -218,6 +222,23 @@ class VectorEnv:
         return (torch.empty(shape, dtype=torch.uint8, device=self.device),
                 torch.empty(shape, dtype=torch.uint8, device=self.device))
 
+    def _arm_reuse(self):
+        """The caller's own buffers were (re)validated: the next launch writes every row, later
+        ones may skip rows that already hold their frame. Also called for buffers seen before:
+        a new tensor at a recycled address must not inherit the old one's record."""
+        if self.reuse_outputs:
+            _lib.check(self.lib.vn_set_output_reuse(self._ctx, 1), "vn_set_output_reuse")
+            self._reuse_on = True
+
+    def _disarm_reuse(self):
+        """Fresh output tensors: the allocator may hand back an address whose record still
+        matches but whose bytes are someone else's, so every row is written. The cached
+        buffers are dropped with it, so the next step(out=...) arms again."""
+        if self._reuse_on:
+            _lib.check(self.lib.vn_set_output_reuse(self._ctx, 0), "vn_set_output_reuse")
+            self._reuse_on = False
+            self._out_cache = None
+
     def reset(self, mask=None):
         m = None
         if mask is not None:
@@ -234,6 +255,10 @@ class VectorEnv:
             return None, None
         img, goal = out if out is not None else self._frames()
         self._check_frames_out(img, goal)
+        if out is None:
+            self._disarm_reuse()
+        else:
+            self._arm_reuse()
         _lib.check(self.lib.vn_observe(self._ctx, _lib.ptr(img), _lib.ptr(goal), None, self._stream()), "vn_observe")
         if self.aux_observations:
             return (img, goal) + self._gather_aux()
@@ -248,7 +273,13 @@ class VectorEnv:
         copied per step and info's tensors (ep_return, ep_length, terminal_state, truncated,
         img_row, goal_row) are the env's own buffers, overwritten by the next step like the
         ``out`` buffers. ``gather=False`` skips the frame copy
-        (index-only step: info img_row / goal_row address the frames in the scene cache)."""
+        (index-only step: info img_row / goal_row address the frames in the scene cache).
+        Contract of ``out`` with ``reuse_outputs=True`` (the default): the step does not copy a
+        frame whose row of ``out["image"]`` / ``out["goal"]`` already holds it from this env's
+        previous step (the goal between resets, the image on a blocked move), so the image and
+        goal rows must be left as the env wrote them until the next step. Rows that are edited
+        in place, shared between two envs or written by anything else need
+        ``VectorEnv(..., reuse_outputs=False)``, which writes every row on every step."""
         if type(actions) is torch.Tensor and actions.dtype == torch.int32 and actions.device == self.device \
                 and actions.shape == (self.num_envs,) and actions.is_contiguous():
             a = actions
@@ -276,6 +307,8 @@ class VectorEnv:
                     return (bufs[0], bufs[1]) + self._gather_aux(), bufs[2], bufs[3], info
                 return (bufs[0], bufs[1]), bufs[2], bufs[3], info
         if out is None:
+            if gather:
+                self._disarm_reuse()
             img, goal = self._frames() if gather else (None, None)
             reward = torch.empty(self.num_envs, dtype=torch.float32, device=self.device)
             done = torch.empty(self.num_envs, dtype=torch.bool, device=self.device)
@@ -291,6 +324,7 @@ class VectorEnv:
                 bufs = (img, goal, reward, done, state)
                 self._out_cache = (bufs, tuple(_lib.ptr(t) for t in bufs),
                                    tuple((t.data_ptr(), t.numel()) if t is not None else None for t in bufs))
+                self._arm_reuse()
         _lib.check(self.lib.vn_step(self._ctx, _lib.ptr(a), _lib.ptr(img), _lib.ptr(goal), _lib.ptr(reward),
                                     _lib.ptr(done), _lib.ptr(state), self._stream()), "vn_step")
         # fresh info tensors unless the caller chose the in-place path (out=...)

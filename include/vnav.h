@@ -115,7 +115,9 @@ int vn_step(vn_ctx* ctx, const int32_t* actions_dev, uint8_t* obs_dev, uint8_t* 
  * in the same launch: the next step's recurrent inputs (last action one-hot and reward,
  * times the episode mask m = 1 - done) and the finished-episode statistics accumulated per
  * env into episode_stats_env [3][E] (count, return sum, length sum; reduced and cleared by
- * vn_a2c_episode_stats). Optional outputs may be NULL. */
+ * vn_a2c_episode_stats). Optional outputs may be NULL. The a2c step is index-only by
+ * construction: it has no frame outputs (the frames are addressed through the img_row /
+ * goal_row info buffers), and its kernel with the heads fused carries no frame-copy code. */
 typedef struct vn_a2c_step {
   const float* policy_out;          /* [E][8] */
   int num_actions;                  /* 1..7 */
@@ -178,6 +180,24 @@ int vn_set_curriculum(vn_ctx* ctx, double complexity, int mode, double offset);
 int vn_set_curriculum_scenes(vn_ctx* ctx, double complexity, const int32_t* modes_host,
                              const double* offsets_host);
 int vn_set_autoreset(vn_ctx* ctx, int on);                /* default on */
+
+/* Output reuse for callers that step into the same obs_dev / goal_dev buffers every call.
+ * The context records, per env and in device memory (stream order), the address of the
+ * image row and of the goal row it last wrote and the arena row whose bytes went there.
+ * With reuse on, a vn_step / vn_observe that gets both buffers skips the copy of a frame
+ * whose destination row is the recorded address and already holds the arena row to emit
+ * (the goal frame between resets; the image on a blocked move or a kept terminal
+ * observation). The kernel cannot see other writers, so this is a contract: with reuse on,
+ * nothing but vn_step / vn_observe of this context writes to those rows between two calls,
+ * and no row is shared by two envs. Off by default (every launch writes every row).
+ * on = 1: the first launch with both buffers after the call still writes every row (call
+ * it again whenever the buffers' contents may have changed hands, e.g. a freshly allocated
+ * buffer at a recycled address); later ones may skip. Host-only, no synchronisation. A
+ * captured launch replays correctly: the records live on the device. A launch that is
+ * captured into a graph while the full write is still armed is recorded as a full write
+ * (every replay of it writes every row) and does not use the arm up: the next launch that
+ * is executed directly still writes every row. */
+int vn_set_output_reuse(vn_ctx* ctx, int on);
 
 /* Synthetic uniform actions in [0,4) from Philox(seed, env, step). */
 int vn_random_actions(vn_ctx* ctx, int32_t* actions_dev, uint64_t step, vn_stream_t stream);
