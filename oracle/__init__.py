@@ -21,4 +21,8 @@ Modules
               the float64 numpy references of the A2C step / update kernels (*64)
   a2c_cases.py  deterministic inputs of the A2C step tests (shared by the GPU tests and
               the CPU check of their draws' distance to the CDF boundaries)
+  trunk_checks.py  the checks the GPU policy tests share: error measures, the activation
+              store's views and ReLU masks, gradients vs the fp64 oracle, the recurrent core
+              vs torch's float64 nn.LSTM
+  few_env_cases.py  case tables and inputs of the few-env / float-frame / 1..7-action tests
 """

@@ -21,6 +21,7 @@ Tolerances (north star): outputs 1e-5, parameter gradients 1e-4 of each tensor's
 Logits and values are also checked element by element: |gpu - fp64| <= 1e-5 |fp64| + a floor
 of 1e-6 of the tensor's scale (a logit near zero is a sum of cancelling terms whose fp32
 rounding is set by the terms, not by the sum: the floor states that absolute bound).
+The checks themselves are oracle/trunk_checks.py, shared with tests/test_few_env_gpu.py.
 """
 import ctypes
 
@@ -29,104 +30,12 @@ import pytest
 import torch
 
 from oracle import a2c as oa2c
-from oracle.policy import (AuxHeadsOracle, GoalNetOracle, aux_targets, frames_to_float, trunk_sizes)
+from oracle.policy import AuxHeadsOracle, GoalNetOracle, aux_targets, frames_to_float
+from oracle.trunk_checks import (AUX_NAMES, NAMES, _check_masks_are_signs, _check_outputs, _elementwise, _err,
+                                 _gpu_masks, _grads_vs_oracle, lstm_core_check)
+from oracle.trunk_checks import a2c_loss_grad as _loss_grad
 
 pytestmark = pytest.mark.gpu
-
-NAMES = {"shared_base.0.0": "conv1", "shared_base.0.2": "conv2", "conv_base.0.0": "conv3",
-         "conv_base.0.2": "conv4", "conv_merge.0.1": "fc", "policy_logits.0": "policy_logits",
-         "critic.0": "critic"}
-AUX_NAMES = ("deconv_depth", "deconv_mask", "deconv_mask_goal")
-
-
-def _err(a, b):
-    a = np.asarray(a, dtype=np.float64)
-    b = np.asarray(b, dtype=np.float64)
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-30)
-
-
-ELEM_RTOL, ELEM_FLOOR = 1e-5, 1e-6
-
-
-def _elementwise(a, b, rtol=ELEM_RTOL, floor=ELEM_FLOOR):
-    """max over elements of |a - b| / (rtol |b| + floor max|b|): <= 1 passes."""
-    a = np.asarray(a, dtype=np.float64)
-    b = np.asarray(b, dtype=np.float64)
-    return float((np.abs(a - b) / (rtol * np.abs(b) + floor * max(np.abs(b).max(), 1e-30))).max())
-
-
-def _check_outputs(o_logits, o_value, logits, value):
-    """Logits / values: normwise 1e-5 of scale and the elementwise bound above."""
-    assert _err(o_logits, logits) <= 1e-5
-    assert _err(o_value, value) <= 1e-5
-    e = (_elementwise(o_logits, logits), _elementwise(o_value, value))
-    assert max(e) <= 1.0, "elementwise logits / values: %.3g / %.3g of the bound" % e
-    return e
-
-
-def _acts_views(net, acts, n):
-    """The activation store the forward wrote (csrc/vn_policy.hip acts_at): [conv1 ReLU
-    bitmask | X1 | X2 | X3 | X4 | X5], each sample-contiguous NHWC, frames 2i (image) and
-    2i + 1 (goal)."""
-    o1, o2, o3 = trunk_sizes(*net.frame_hw)
-    msz = 2 * o1[0] * o1[1]
-    sz = [2 * o1[0] * o1[1] * 32, 2 * o2[0] * o2[1] * 32, o3[0] * o3[1] * 64, o3[0] * o3[1] * 32, 512]
-    assert net.act_floats == msz + sum(sz)
-    out = {"M1": acts[:n * msz].view(torch.int32).view(n, 2, o1[0], o1[1])}
-    p = n * msz
-    shapes = [(n, 2, o1[0], o1[1], 32), (n, 2, o2[0], o2[1], 32), (n, o3[0], o3[1], 64), (n, o3[0], o3[1], 32),
-              (n, 512)]
-    for i, sh in enumerate(shapes):
-        out["X%d" % (i + 1)] = acts[p:p + n * sz[i]].view(sh)
-        p += n * sz[i]
-    return out
-
-
-def _gpu_masks(net, acts, n):
-    """0/1 float64 masks (NCHW) of every trunk ReLU from the GPU's activations; checks that
-    conv1's channel bitmask (what conv2's input gradient reads) equals X1 > 0."""
-    v = _acts_views(net, acts, n)
-    x1 = v["X1"] > 0
-    bits = (v["M1"][..., None] >> torch.arange(32, device=acts.device, dtype=torch.int32)) & 1
-    assert torch.equal(bits.bool(), x1), "conv1 ReLU bitmask != X1 > 0"
-
-    def nchw(t):
-        return t.permute(0, 3, 1, 2).double().cpu()
-    return {"m1i": nchw(x1[:, 0]), "m1g": nchw(x1[:, 1]), "m2i": nchw(v["X2"][:, 0] > 0),
-            "m2g": nchw(v["X2"][:, 1] > 0), "m3": nchw(v["X3"] > 0), "m4": nchw(v["X4"] > 0),
-            "m5": (v["X5"] > 0).double().cpu()}
-
-
-def _check_masks_are_signs(masks, pre):
-    """A mask bit may differ from the sign of the oracle's pre-activation only at a tie."""
-    pairs = {"m1i": "z1i", "m1g": "z1g", "m2i": "z2i", "m2g": "z2g", "m3": "z3", "m4": "z4", "m5": "z5"}
-    flips = {}
-    for m, z in pairs.items():
-        zz = pre[z].detach()
-        bad = (masks[m] > 0) != (zz > 0)
-        if bad.any():
-            worst = float(zz[bad].abs().max() / zz.abs().max())
-            assert worst <= 1e-5, "%s: mask disagrees with the oracle's sign at |z| = %.3g of scale" % (m, worst)
-        flips[m] = int(bad.sum())
-    return flips
-
-
-def _grads_vs_oracle(net, grads, ref, heads=None, tol=1e-4):
-    mine = net.to_reference(grads)
-    errs = {}
-    for k, attr in NAMES.items():
-        mod = getattr(ref, attr)
-        for kind in ("weight", "bias"):
-            errs[k + "." + kind] = _err(mine[k + "." + kind].numpy(), getattr(mod, kind).grad.numpy())
-    if heads is not None:
-        for h, name in zip(heads.heads, AUX_NAMES):
-            for i, layer in ((1, h[0]), (3, h[2])):
-                for kind in ("weight", "bias"):
-                    key = "%s.0.%d.%s" % (name, i, kind)
-                    errs[key] = _err(mine[key].numpy(), getattr(layer, kind).grad.numpy())
-    bad = {k: "%.3g" % e for k, e in errs.items() if e > tol}
-    assert not bad, bad
-    return max(errs.values())
 
 
 def _noisy_policy(hw, seed, aux=False):
@@ -144,18 +53,6 @@ def _noisy_policy(hw, seed, aux=False):
             w2.mul_(m[:, None, None, :])
             b2[7] = 0.0
     return pol
-
-
-def _loss_grad(out, actions, rets):
-    from vnav import _lib
-    lib = _lib.load()
-    n = out.shape[0]
-    dout = torch.zeros_like(out)
-    stats = torch.zeros(4, dtype=torch.float32, device=out.device)
-    _lib.check(lib.vn_a2c_loss_grad(_lib.ptr(out), _lib.ptr(actions), _lib.ptr(rets), n, 4, ctypes.c_float(0.5),
-                                    ctypes.c_float(0.01), _lib.ptr(dout), _lib.ptr(stats),
-                                    _lib.stream_ptr(out.device)), "vn_a2c_loss_grad")
-    return dout
 
 
 def test_84_batch4096_forward_backward_vs_fp64_oracle():
@@ -295,80 +192,7 @@ def test_lstm_core_vs_fp64_torch_lstm(E):
     (h, c), the heads on h, and the gradients of W_ih, W_hh, both biases, the heads and
     dL/dZ5 (masked by the features' ReLU) vs torch's float64 nn.LSTM with the restated
     MaskedRNN convention."""
-    from vnav.policy import PolicyNet
-    net = PolicyNet((84, 84), 4, recurrent=True)
-    params = net.init_params(3)
-    with torch.no_grad():
-        params.add_(torch.randn(params.shape, generator=torch.Generator().manual_seed(2)).cuda() * 0.01)
-    T, A = 3, 4
-    N = T * E
-    L = net.lstm
-    g = torch.Generator(device="cuda").manual_seed(4)
-    x5 = torch.relu(torch.randn((N, 512), device="cuda", generator=g))
-    lra = torch.zeros((T, E, A + 1), device="cuda")
-    lra[..., :A].scatter_(2, torch.randint(0, A, (T, E, 1), device="cuda", generator=g), 1.0)
-    lra[..., A] = (torch.rand((T, E), device="cuda", generator=g) < 0.1).float()
-    masks = (torch.rand((T, E), device="cuda", generator=g) > 0.05).float()
-    lra *= masks[..., None]
-    h0 = torch.randn((E, 512), device="cuda", generator=g) * 0.5
-    c0 = torch.randn((E, 512), device="cuda", generator=g) * 0.5
-    xcat = torch.zeros((N, L["xcat"]), device="cuda")
-    la = torch.zeros((N, 2048), device="cuda")
-    c_all = torch.zeros((N, 512), device="cuda")
-    h_all = torch.zeros((N, 512), device="cuda")
-    gates = torch.zeros((E, 2048), device="cuda")
-    out = torch.zeros((N, 8), device="cuda")
-    for t in range(T):
-        sl = slice(t * E, (t + 1) * E)
-        hp = h0 if t == 0 else h_all[(t - 1) * E:t * E]
-        cp = c0 if t == 0 else c_all[(t - 1) * E:t * E]
-        net.lstm_step(params, E, x5[sl], lra[t], masks[t], hp, cp, xcat[sl], gates, la[sl], c_all[sl], h_all[sl])
-    net.heads(params, h_all, N, out)
-    actions = torch.randint(0, A, (N,), dtype=torch.int32, device="cuda", generator=g)
-    rets = torch.randn(N, device="cuda", generator=g)
-    dout = _loss_grad(out, actions, rets)
-    grads = torch.zeros_like(params)
-    dz5 = torch.zeros((N, 512), device="cuda")
-    ws = torch.empty(net.lstm_workspace_floats(T, E), device="cuda")
-    net.lstm_backward(params, T, E, dout, h_all, xcat, la, c_all, c0, masks, x5, dz5, grads, ws)
-    torch.cuda.synchronize()
-
-    sd = net.to_reference(params)
-    lstm = torch.nn.LSTM(512 + A + 1, 512, batch_first=True).double()
-    for name in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
-        getattr(lstm, name).data.copy_(sd["rnn.inner." + name].double())
-    pl = torch.nn.Linear(512, A).double()
-    cr = torch.nn.Linear(512, 1).double()
-    for mod, k in ((pl, "policy_logits.0"), (cr, "critic.0")):
-        mod.weight.data.copy_(sd[k + ".weight"].double())
-        mod.bias.data.copy_(sd[k + ".bias"].double())
-    xf = x5.cpu().double().view(T, E, 512).requires_grad_()
-    x = torch.cat((xf, lra.cpu().double()), 2)
-    h, c = h0.cpu().double()[None], c0.cpu().double()[None]
-    m = masks.cpu().double()
-    ys, cs = [], []
-    for t in range(T):
-        y, (h, c) = lstm(x[t][:, None], (h * m[t][None, :, None], c * m[t][None, :, None]))
-        ys.append(y[:, 0])
-        cs.append(c[0])
-    y = torch.cat(ys)
-    assert _err(h_all.cpu().numpy(), y.detach().numpy()) <= 1e-5
-    assert _err(c_all.cpu().numpy(), torch.cat(cs).detach().numpy()) <= 1e-5
-    logits, value = pl(y), cr(y)
-    o = out.cpu().numpy()
-    _check_outputs(o[:, :4], o[:, 4], logits.detach().numpy(), value.detach().numpy().ravel())
-    loss, _ = oa2c.loss(logits, value.view(-1), actions.cpu().long(), rets.cpu().double())
-    loss.backward()
-    mine = net.to_reference(grads)
-    errs = {"dz5": _err(dz5.cpu().numpy(), (xf.grad * (xf > 0)).reshape(N, 512).detach().numpy())}
-    for name in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
-        errs[name] = _err(mine["rnn.inner." + name].numpy(), getattr(lstm, name).grad.numpy())
-    for mod, k in ((pl, "policy_logits.0"), (cr, "critic.0")):
-        errs[k + ".weight"] = _err(mine[k + ".weight"].numpy(), mod.weight.grad.numpy())
-        errs[k + ".bias"] = _err(mine[k + ".bias"].numpy(), mod.bias.grad.numpy())
-    bad = {k: "%.3g" % e for k, e in errs.items() if e > 1e-4}
-    assert not bad, bad
-    print("LSTM E=%d T=3: worst gradient error %.3g of scale" % (E, max(errs.values())))
+    lstm_core_check(E, T=3, A=4)
 
 
 def test_logged_run_shape_trainer_update_vs_fp64_oracle():
