@@ -10,11 +10,18 @@
 // observation replaces the terminal one) under gym's TimeLimit(900).
 //
 // Design (DESIGN.md "vn_step"): one wave64 per env, 4 envs per 256-thread workgroup.
-// The per-env state is wave-uniform (scalar loads); a reset runs 64 Philox start
-// candidates in parallel, one per lane, and a wave ballot picks the first valid one —
-// the same result as the sequential rejection loop over the same counter stream.
-// The two frames are then streamed with 16-B lanes, 8 loads in flight per lane; with output
-// reuse on (vn_set_output_reuse) a frame whose output row already holds it is not copied.
+// Everything an env carries from launch to launch is one 128-B record (EnvRec): the seven
+// state words, the running return, the four graph neighbours of the current state, the
+// scene fields a step needs (row bases, graph offset, terminal_obs, the three rewards) and
+// the output-reuse record. A wave reads it with two wide scalar loads issued together with
+// actions[e]; one round trip later it knows the next state and the arena rows to emit, and
+// the frame loads issue at once. Lane 0 writes the record back (wide vector stores) and the
+// scalar outputs after the first frame loads are in flight. Only a reset (rare) reads the
+// scene table again and refreshes the cached fields. A reset runs 64 Philox start candidates
+// in parallel, one per lane, and a wave ballot picks the first valid one - the same result
+// as the sequential rejection loop over the same counter stream.
+// The frames are streamed with 16-B lanes, 8 loads in flight per lane; with output reuse on
+// (vn_set_output_reuse) a frame whose output row already holds it is not copied.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -56,14 +63,40 @@ struct SceneDev {
 
 enum { ST_SCENE = 0, ST_STATE, ST_GOAL, ST_OBS, ST_ELAPSED, ST_EPISODE, ST_SCHED, ST_COUNT };
 
+// The per-env record, as 32-bit words (floats as their bits). Words 0..17 are what a step
+// reads and, up to word 11, rewrites; 12..17 change only when a reset changes the scene.
+enum {
+  RW_ST = 0,          // [ST_COUNT] state words, in vn_get_state's order
+  RW_RET = 7,         // running return of the unfinished episode (f32)
+  RW_NB = 8,          // [4] graph[state][0..3] of the current scene
+  RW_ROW_BASE = 12,   // SceneDev::row_base
+  RW_COMP_BASE = 13,  // SceneDev::comp_base (-1 = none)
+  RW_GRAPH_TOBS = 14, // SceneDev::graph_off << 1 | (terminal_obs != 0)
+  RW_R_GOAL = 15,     // the scene's three rewards (f32)
+  RW_R_STEP = 16,
+  RW_R_COLL = 17,
+  RW_OUT_ROW = 18,    // [2] arena row last written to the image / goal output row
+  RW_OUT_ADDR = 20,   // [2] x 64 bit: that output row's address (0 matches nothing)
+  RW_USED = 24,
+  RW_WORDS = 32,
+};
+struct alignas(128) EnvRec {
+  int32_t w[RW_WORDS];
+};
+static_assert(sizeof(EnvRec) == 128, "one record per 128-B line");
+
+typedef int32_t i32x16 __attribute__((ext_vector_type(16), may_alias, aligned(64)));
+typedef int32_t i32x8 __attribute__((ext_vector_type(8), may_alias, aligned(32)));
+typedef int32_t i32x4 __attribute__((ext_vector_type(4), may_alias, aligned(16)));
+typedef int32_t i32x2 __attribute__((ext_vector_type(2), may_alias, aligned(8)));
+
 struct EnvArgs {
   const SceneDev* scenes;
   const int32_t* graph;
   const int32_t* spd;
   const uint8_t* arena;
   int64_t frame_bytes;
-  int32_t* st;  // [ST_COUNT][n_envs]
-  float* ep_ret;
+  EnvRec* recs;  // [n_envs]
   const int32_t* env_scene;
   const int32_t* tasks;
   const int32_t* sched;
@@ -104,10 +137,8 @@ struct EnvArgs {
   const float* head_b;
   const float* head_x;
   float* head_out;
-  // output reuse (DESIGN.md "vn_step: output reuse"): what each env last wrote, and whether
-  // this launch may skip a frame whose destination row already holds it
-  uint64_t* rec_addr;  // [2][n_envs] destination address of the last image / goal row written
-  int32_t* rec_row;    // [2][n_envs] arena row whose bytes went there
+  // output reuse (DESIGN.md "vn_step: output reuse"): whether this launch may skip a frame
+  // whose destination row already holds it (the record's RW_OUT_* words say what it holds)
   int reuse;
 };
 
@@ -119,11 +150,9 @@ constexpr int kStartRounds = 16;  // 1024 rejection attempts before flagging
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-// Wave-cooperative reset of env e (all 64 lanes call with uniform arguments).
-__device__ void reset_env(const EnvArgs& a, int e, int lane, int& sc, int& s, int& g) {
-  const int n_envs = a.n_envs;
-  const int k = a.st[ST_EPISODE * n_envs + e];
-  const int sp = a.st[ST_SCHED * n_envs + e];
+// Wave-cooperative reset of env e (all 64 lanes call with uniform arguments). k is the env's
+// reset count, sp its schedule position (advanced here when the schedule supplies the pair).
+__device__ void reset_env(const EnvArgs& a, int e, int lane, int k, int& sp, int& sc, int& s, int& g) {
   if (a.sched_len > 0 && sp < a.sched_len) {
     sc = a.env_scene[e];
     const int n = a.scenes[sc].n;
@@ -134,7 +163,7 @@ __device__ void reset_env(const EnvArgs& a, int e, int lane, int& sc, int& s, in
       s = min(max(s, 0), n - 1);
       g = min(max(g, 0), n - 1);
     }
-    if (lane == 0) a.st[ST_SCHED * n_envs + e] = sp + 1;
+    sp += 1;
     return;
   }
   const u32x4 rg = philox4x32_10(u32x4{(uint32_t)e, (uint32_t)k, 0u, STREAM_GOAL}, a.k0, a.k1);
@@ -188,6 +217,10 @@ __device__ void reset_env(const EnvArgs& a, int e, int lane, int& sc, int& s, in
 // the bench, tools/ab/copy_variants.sh): at 4096 envs default stores 57-60 us, any single nt
 // stream 54-56 us; at 32768 envs per GPU nt on both stores 446 us (6.2 TB/s) vs 551 us
 // default and 545-563 us with nt loads; nt on all four streams is the slowest everywhere.
+//
+// Both copy routines take `mid`, the wave's scalar work (lane 0's record and output stores):
+// it runs once, after the first trip's loads are issued and before their data is waited
+// for, so the first frame-data wait does not sit behind those stores' acknowledgements.
 __device__ __forceinline__ void st16_nt(uint4* p, const uint4 v) {
   __builtin_nontemporal_store(v.x, &p->x);
   __builtin_nontemporal_store(v.y, &p->y);
@@ -195,10 +228,10 @@ __device__ __forceinline__ void st16_nt(uint4* p, const uint4 v) {
   __builtin_nontemporal_store(v.w, &p->w);
 }
 
-template <int VEC>
+template <int VEC, class Mid>
 __device__ __forceinline__ void copy_two_frames(uint8_t* __restrict__ d1, const uint8_t* __restrict__ s1,
                                                 uint8_t* __restrict__ d2, const uint8_t* __restrict__ s2,
-                                                int64_t bytes, int lane) {
+                                                int64_t bytes, int lane, Mid mid) {
   if constexpr (VEC == 16) {
     constexpr int U = 4;
     const int n = (int)(bytes >> 4);
@@ -207,6 +240,25 @@ __device__ __forceinline__ void copy_two_frames(uint8_t* __restrict__ d1, const 
     uint4* x = reinterpret_cast<uint4*>(d1);
     uint4* y = reinterpret_cast<uint4*>(d2);
     int i = lane;
+    {  // first trip, mid() inside it. Its U loads per stream are always issued, so the number
+       // in flight at mid() is fixed. A frame shorter than one trip (n < 64 U) reads its first
+       // chunks as a stand-in and is copied by the loops below
+      const bool full = 64 * U <= n;  // wave-uniform
+      const int i0 = full ? lane : min(lane, n - 1), step = full ? 64 : 0;
+      uint4 va[U], vb[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) va[u] = a[i0 + step * u];
+#pragma unroll
+      for (int u = 0; u < U; ++u) vb[u] = b[i0 + step * u];
+      mid();
+      if (full) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) st16_nt(x + i + 64 * u, va[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u) st16_nt(y + i + 64 * u, vb[u]);
+        i += 64 * U;
+      }
+    }
     for (; i + 64 * (U - 1) < n; i += 64 * U) {
       uint4 va[U], vb[U];
 #pragma unroll
@@ -224,6 +276,7 @@ __device__ __forceinline__ void copy_two_frames(uint8_t* __restrict__ d1, const 
       st16_nt(y + i, b0);
     }
   } else if constexpr (VEC == 4) {
+    mid();
     const int n = (int)(bytes >> 2);
     const uint32_t* a = reinterpret_cast<const uint32_t*>(s1);
     const uint32_t* b = reinterpret_cast<const uint32_t*>(s2);
@@ -235,6 +288,7 @@ __device__ __forceinline__ void copy_two_frames(uint8_t* __restrict__ d1, const 
       y[i] = b0;
     }
   } else {
+    mid();
     for (int64_t i = lane; i < bytes; i += 64) {
       d1[i] = s1[i];
       d2[i] = s2[i];
@@ -246,15 +300,28 @@ __device__ __forceinline__ void copy_two_frames(uint8_t* __restrict__ d1, const 
 // in flight per lane as copy_two_frames, on one stream. The trip count is wave-uniform; the
 // remainder (1323 uint4 per 84x84x3 frame = 2 trips of 512 + 299) issues all its predicated
 // loads before its stores.
-template <int VEC>
+template <int VEC, class Mid>
 __device__ __forceinline__ void copy_one_frame(uint8_t* __restrict__ d, const uint8_t* __restrict__ s,
-                                               int64_t bytes, int lane) {
+                                               int64_t bytes, int lane, Mid mid) {
   if constexpr (VEC == 16) {
     constexpr int U = 8;
     const int n = (int)(bytes >> 4);
     const uint4* a = reinterpret_cast<const uint4*>(s);
     uint4* x = reinterpret_cast<uint4*>(d);
     int base = 0;
+    {  // first trip, mid() inside it: always U loads (see copy_two_frames)
+      const bool full = 64 * U <= n;  // wave-uniform
+      const int i0 = full ? lane : min(lane, n - 1), step = full ? 64 : 0;
+      uint4 v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[u] = a[i0 + step * u];
+      mid();
+      if (full) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) st16_nt(x + lane + 64 * u, v[u]);
+        base = 64 * U;
+      }
+    }
     for (; base + 64 * U <= n; base += 64 * U) {
       const int i = base + lane;
       uint4 v[U];
@@ -274,13 +341,36 @@ __device__ __forceinline__ void copy_one_frame(uint8_t* __restrict__ d, const ui
         if (i + 64 * u < n) st16_nt(x + i + 64 * u, v[u]);
     }
   } else if constexpr (VEC == 4) {
+    mid();
     const int n = (int)(bytes >> 2);
     const uint32_t* a = reinterpret_cast<const uint32_t*>(s);
     uint32_t* x = reinterpret_cast<uint32_t*>(d);
     for (int i = lane; i < n; i += 64) x[i] = a[i];
   } else {
+    mid();
     for (int64_t i = lane; i < bytes; i += 64) d[i] = s[i];
   }
+}
+
+// The scene fields a record caches (a reset or vn_set_state may change the env's scene).
+struct SceneCache {
+  int32_t row_base, comp_base;
+  uint32_t graph_tobs;
+  float r_goal, r_step, r_coll;
+};
+__device__ __forceinline__ SceneCache scene_cache(const SceneDev& S) {
+  return SceneCache{(int32_t)S.row_base, (int32_t)S.comp_base,
+                    ((uint32_t)S.graph_off << 1) | (S.terminal_obs != 0 ? 1u : 0u), S.r_goal, S.r_step, S.r_coll};
+}
+__device__ __forceinline__ void store_scene_cache(EnvRec* R, const SceneCache& c) {
+  *reinterpret_cast<i32x4*>(R->w + RW_ROW_BASE) =
+      i32x4{c.row_base, c.comp_base, (int32_t)c.graph_tobs, __float_as_int(c.r_goal)};
+  *reinterpret_cast<i32x2*>(R->w + RW_R_STEP) = i32x2{__float_as_int(c.r_step), __float_as_int(c.r_coll)};
+}
+__device__ __forceinline__ void store_out_record(EnvRec* R, int32_t row1, int32_t row2, uint64_t a1, uint64_t a2) {
+  *reinterpret_cast<i32x2*>(R->w + RW_OUT_ROW) = i32x2{row1, row2};
+  *reinterpret_cast<i32x4*>(R->w + RW_OUT_ADDR) =
+      i32x4{(int32_t)(uint32_t)a1, (int32_t)(uint32_t)(a1 >> 32), (int32_t)(uint32_t)a2, (int32_t)(uint32_t)(a2 >> 32)};
 }
 
 template <int MODE, int VEC>
@@ -289,27 +379,32 @@ __global__ __launch_bounds__(256) void env_kernel(EnvArgs a) {
   const int e = uni(blockIdx.x * kEnvsPerBlock + (threadIdx.x >> 6));
   if (e >= a.n_envs) return;
   const int n_envs = a.n_envs;
-  int32_t* st = a.st;
+  EnvRec* R = a.recs + e;
 
-  int sc = st[ST_SCENE * n_envs + e];
-  int s = st[ST_STATE * n_envs + e];
-  int g = st[ST_GOAL * n_envs + e];
-  int os = st[ST_OBS * n_envs + e];
-  // this env's output record, loaded with the state (wave-uniform, before any store of the
-  // kernel); only a launch that may skip frames reads it
-  uint64_t rec_a1 = 0, rec_a2 = 0;
-  int32_t rec_r1 = -1, rec_r2 = -1;
-  if (MODE != MODE_STEP_HEADS && a.reuse) {
-    rec_a1 = a.rec_addr[e];
-    rec_a2 = a.rec_addr[n_envs + e];
-    rec_r1 = a.rec_row[e];
-    rec_r2 = a.rec_row[n_envs + e];
+  // the whole record, wave-uniform, in two scalar loads issued together (before any store
+  // of the wave)
+  const i32x16 lo = *reinterpret_cast<const i32x16*>(R->w);
+  const i32x8 hi = *reinterpret_cast<const i32x8*>(R->w + 16);
+  int sc = lo[ST_SCENE], s = lo[ST_STATE], g = lo[ST_GOAL], os = lo[ST_OBS];
+  int t = lo[ST_ELAPSED], ep = lo[ST_EPISODE], sp = lo[ST_SCHED];
+  SceneCache C{lo[RW_ROW_BASE], lo[RW_COMP_BASE], (uint32_t)lo[RW_GRAPH_TOBS], __int_as_float(lo[RW_R_GOAL]),
+               __int_as_float(hi[RW_R_STEP - 16]), __int_as_float(hi[RW_R_COLL - 16])};
+  const int32_t rec_r1 = hi[RW_OUT_ROW - 16], rec_r2 = hi[RW_OUT_ROW + 1 - 16];
+  const uint64_t rec_a1 = (uint32_t)hi[RW_OUT_ADDR - 16] | ((uint64_t)(uint32_t)hi[RW_OUT_ADDR + 1 - 16] << 32);
+  const uint64_t rec_a2 = (uint32_t)hi[RW_OUT_ADDR + 2 - 16] | ((uint64_t)(uint32_t)hi[RW_OUT_ADDR + 3 - 16] << 32);
+
+  // the caller's action, loaded together with the record (vn_step_a2c samples its own)
+  int act_in = 0;
+  if constexpr (MODE == MODE_STEP) {
+    if (a.actions) act_in = a.actions[e];
   }
 
+  // what lane 0 stores once the frame address is known (MODE_STEP / MODE_STEP_HEADS)
+  bool scene_changed = false, bad = false, done = false, limit = false, terminal = false;
+  int act = 0, term_state = 0, ep_len = 0;
+  float r = 0.0f, ret = 0.0f, new_ret = 0.0f;
+
   if constexpr (MODE == MODE_STEP || MODE == MODE_STEP_HEADS) {
-    int t = st[ST_ELAPSED * n_envs + e];
-    const SceneDev S = a.scenes[sc];
-    int act;
     if (a.pol_out) {  // the policy's categorical draw for this env (vn_policy_sample_dev's)
       float lg[7], p[7], lp[7], H;
       if constexpr (MODE == MODE_STEP_HEADS) {
@@ -357,39 +452,71 @@ __global__ __launch_bounds__(256) void env_kernel(EnvArgs a) {
       const uint64_t ctr = a.pctr + (a.pctr_dev ? (uint64_t)*a.pctr_dev : 0ull);
       act = uni(sample_action(lg, a.pol_A, a.pk0, a.pk1, ctr, (uint32_t)e, p, lp, H));
     } else {
-      act = a.actions[e];
+      act = act_in;
     }
-    const bool bad = (unsigned)act > 3u;
+    // the transition comes from the record's cached neighbours: no graph load on this path
+    bad = (unsigned)act > 3u;
     int nxt = -1;
-    if (!bad) nxt = a.graph[((int64_t)S.graph_off + s) * 4 + act];
+    if (!bad) nxt = act == 0 ? lo[RW_NB] : act == 1 ? lo[RW_NB + 1] : act == 2 ? lo[RW_NB + 2] : lo[RW_NB + 3];
     const bool collided = nxt == -1;
     if (!collided) s = nxt;
-    const bool terminal = (s == g);
-    float r = S.r_step;
-    if (terminal) r = S.r_goal;
-    if (collided) r = S.r_coll;
-    if (!terminal || S.terminal_obs) os = s;
+    terminal = (s == g);
+    r = C.r_step;
+    if (terminal) r = C.r_goal;
+    if (collided) r = C.r_coll;
+    if (!terminal || (C.graph_tobs & 1u)) os = s;
     t += 1;
-    const bool limit = a.max_steps > 0 && t >= a.max_steps;
-    const bool done = terminal || limit;
-    const float ret = a.ep_ret[e] + r;
-    const int term_state = os;
-    const int ep_len = t;
-    float new_ret = ret;
-    if (done && a.autoreset) {
-      reset_env(a, e, lane, sc, s, g);
+    limit = a.max_steps > 0 && t >= a.max_steps;
+    done = terminal || limit;
+    ret = __int_as_float(lo[RW_RET]) + r;
+    term_state = os;
+    ep_len = t;
+    new_ret = ret;
+    if (done && a.autoreset) {  // rare: the slower path re-reads the scene table
+      reset_env(a, e, lane, ep, sp, sc, s, g);
       os = s;
       t = 0;
+      ep += 1;
       new_ret = 0.0f;
+      C = scene_cache(a.scenes[sc]);
+      scene_changed = true;
     }
-    if (lane == 0) {
-      st[ST_SCENE * n_envs + e] = sc;
-      st[ST_STATE * n_envs + e] = s;
-      st[ST_GOAL * n_envs + e] = g;
-      st[ST_OBS * n_envs + e] = os;
-      st[ST_ELAPSED * n_envs + e] = t;
-      if (done && a.autoreset) st[ST_EPISODE * n_envs + e] += 1;
-      a.ep_ret[e] = new_ret;
+  } else if constexpr (MODE == MODE_RESET) {
+    if (a.mask == nullptr || a.mask[e] != 0) {
+      reset_env(a, e, lane, ep, sp, sc, s, g);
+      C = scene_cache(a.scenes[sc]);
+      const i32x4 nb = *reinterpret_cast<const i32x4*>(a.graph + ((int64_t)(C.graph_tobs >> 1) + s) * 4);
+      if (lane == 0) {
+        *reinterpret_cast<i32x4*>(R->w + 0) = i32x4{sc, s, g, s};
+        *reinterpret_cast<i32x4*>(R->w + 4) = i32x4{0, ep + 1, sp, __float_as_int(0.0f)};
+        *reinterpret_cast<i32x4*>(R->w + RW_NB) = nb;
+        store_scene_cache(R, C);
+      }
+    }
+    return;
+  }
+
+  // the new state's neighbours, for the next step's record: needed only by lane 0's stores,
+  // which follow the first frame loads
+  i32x4 nb = i32x4{lo[RW_NB], lo[RW_NB + 1], lo[RW_NB + 2], lo[RW_NB + 3]};
+  if constexpr (MODE == MODE_STEP || MODE == MODE_STEP_HEADS)
+    nb = *reinterpret_cast<const i32x4*>(a.graph + ((int64_t)(C.graph_tobs >> 1) + s) * 4);
+
+  const int32_t img_row = C.row_base + os, goal_row = C.comp_base >= 0 ? C.comp_base + os : C.row_base + g;
+
+  // lane 0's stores: the record, the step's scalar outputs, the a2c bookkeeping. row1/row2,
+  // addr1/addr2: the output record to leave (written when `out_rec`).
+  auto emit = [&](bool out_rec, int32_t row1, int32_t row2, uint64_t addr1, uint64_t addr2)
+                  __attribute__((always_inline)) {
+    if (lane != 0) return;
+    if constexpr (MODE == MODE_STEP || MODE == MODE_STEP_HEADS) {
+      *reinterpret_cast<i32x4*>(R->w + 0) = i32x4{sc, s, g, os};
+      *reinterpret_cast<i32x4*>(R->w + 4) = i32x4{t, ep, sp, __float_as_int(new_ret)};
+      *reinterpret_cast<i32x4*>(R->w + RW_NB) = nb;
+      if (scene_changed) store_scene_cache(R, C);
+    }
+    if (out_rec) store_out_record(R, row1, row2, addr1, addr2);
+    if constexpr (MODE == MODE_STEP || MODE == MODE_STEP_HEADS) {
       if (bad) atomicOr(a.flags, (uint32_t)VN_FLAG_BAD_ACTION);
       if (a.reward) a.reward[e] = r;
       if (a.done) a.done[e] = done ? 1 : 0;
@@ -398,6 +525,12 @@ __global__ __launch_bounds__(256) void env_kernel(EnvArgs a) {
       if (a.info_len) a.info_len[e] = ep_len;
       if (a.info_term) a.info_term[e] = term_state;
       if (a.info_trunc) a.info_trunc[e] = (limit && !terminal) ? 1 : 0;
+    } else {
+      if (a.state_out) a.state_out[e] = s;
+    }
+    if (a.info_img_row) a.info_img_row[e] = img_row;
+    if (a.info_goal_row) a.info_goal_row[e] = goal_row;
+    if constexpr (MODE == MODE_STEP || MODE == MODE_STEP_HEADS) {
       if (a.pol_out) {  // vn_a2c_step_post's bookkeeping for this env
         const float m = done ? 0.0f : 1.0f;
         a.act_out[e] = act;
@@ -416,65 +549,75 @@ __global__ __launch_bounds__(256) void env_kernel(EnvArgs a) {
         }
       }
     }
-  } else if constexpr (MODE == MODE_RESET) {
-    if (a.mask == nullptr || a.mask[e] != 0) {
-      reset_env(a, e, lane, sc, s, g);
-      os = s;
-      if (lane == 0) {
-        st[ST_SCENE * n_envs + e] = sc;
-        st[ST_STATE * n_envs + e] = s;
-        st[ST_GOAL * n_envs + e] = g;
-        st[ST_OBS * n_envs + e] = os;
-        st[ST_ELAPSED * n_envs + e] = 0;
-        st[ST_EPISODE * n_envs + e] += 1;
-        a.ep_ret[e] = 0.0f;
-      }
-    }
-    return;
-  } else {
-    if (lane == 0 && a.state_out) a.state_out[e] = s;
-  }
+  };
 
-  const int64_t base = a.scenes[sc].row_base, comp = a.scenes[sc].comp_base;
-  const int64_t img_row = base + os, goal_row = comp >= 0 ? comp + os : base + g;
-  if (lane == 0) {
-    if (a.info_img_row) a.info_img_row[e] = (int32_t)img_row;
-    if (a.info_goal_row) a.info_goal_row[e] = (int32_t)goal_row;
+  if constexpr (MODE == MODE_STEP_HEADS) {  // vn_step_a2c is index-only: no frame tail
+    emit(false, 0, 0, 0, 0);
+    return;
   }
-  if constexpr (MODE == MODE_STEP_HEADS) return;  // vn_step_a2c is index-only: no frame tail
   if (a.obs != nullptr && a.goal_out != nullptr) {
     const int64_t F = a.frame_bytes;
     uint8_t* d1 = a.obs + (int64_t)e * F;
     uint8_t* d2 = a.goal_out + (int64_t)e * F;
     // a frame is skipped when this env's last write to the same row put the same arena row
     // there (the caller leaves the rows alone in between: vn_set_output_reuse's contract)
-    const bool keep1 = a.reuse && rec_a1 == (uint64_t)d1 && rec_r1 == (int32_t)img_row;
-    const bool keep2 = a.reuse && rec_a2 == (uint64_t)d2 && rec_r2 == (int32_t)goal_row;
-    if (!keep1 && !keep2)
-      copy_two_frames<VEC>(d1, a.arena + img_row * F, d2, a.arena + goal_row * F, F, lane);
-    else if (!keep1)
-      copy_one_frame<VEC>(d1, a.arena + img_row * F, F, lane);
-    else if (!keep2)
-      copy_one_frame<VEC>(d2, a.arena + goal_row * F, F, lane);
-    if (lane == 0) {
-      a.rec_addr[e] = (uint64_t)d1;
-      a.rec_addr[n_envs + e] = (uint64_t)d2;
-      a.rec_row[e] = (int32_t)img_row;
-      a.rec_row[n_envs + e] = (int32_t)goal_row;
+    const bool keep1 = a.reuse && rec_a1 == (uint64_t)d1 && rec_r1 == img_row;
+    const bool keep2 = a.reuse && rec_a2 == (uint64_t)d2 && rec_r2 == goal_row;
+    auto mid = [&]() __attribute__((always_inline)) { emit(true, img_row, goal_row, (uint64_t)d1, (uint64_t)d2); };
+    if (!keep1 && !keep2) {
+      copy_two_frames<VEC>(d1, a.arena + (int64_t)img_row * F, d2, a.arena + (int64_t)goal_row * F, F, lane, mid);
+    } else if (!keep1 || !keep2) {
+      uint8_t* d = keep1 ? d2 : d1;
+      const int32_t row = keep1 ? goal_row : img_row;
+      copy_one_frame<VEC>(d, a.arena + (int64_t)row * F, F, lane, mid);
+    } else {
+      mid();
     }
   } else if (a.obs != nullptr || a.goal_out != nullptr) {
     const int64_t F = a.frame_bytes;
     const int k = a.obs ? 0 : 1;  // which frame: always copied, its record updated
     uint8_t* d = (k == 0 ? a.obs : a.goal_out) + (int64_t)e * F;
-    const uint8_t* src = a.arena + (k == 0 ? img_row : goal_row) * F;
+    const uint8_t* src = a.arena + (int64_t)(k == 0 ? img_row : goal_row) * F;
+    // the other frame's record no longer holds if this row was its destination
+    const uint64_t oa = k == 0 ? rec_a2 : rec_a1;
+    const uint64_t other = oa == (uint64_t)d ? 0 : oa;
+    if (k == 0)
+      emit(true, img_row, rec_r2, (uint64_t)d, other);
+    else
+      emit(true, rec_r1, goal_row, other, (uint64_t)d);
     for (int64_t i = lane; i < F; i += 64) d[i] = src[i];
-    if (lane == 0) {
-      a.rec_addr[k * n_envs + e] = (uint64_t)d;
-      a.rec_row[k * n_envs + e] = (int32_t)(k == 0 ? img_row : goal_row);
-      // the other frame's record no longer holds if this row was its destination
-      if (a.rec_addr[(1 - k) * n_envs + e] == (uint64_t)d) a.rec_addr[(1 - k) * n_envs + e] = 0;
-    }
+  } else {
+    emit(false, 0, 0, 0, 0);
   }
+}
+
+// vn_get_state / vn_get_episode_returns: dst[f][e] = word (w0 + f) of env e's record.
+__global__ void rec_gather_kernel(const EnvRec* recs, int n_envs, int w0, int nw, int32_t* dst) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_envs) return;
+  for (int f = 0; f < nw; ++f) dst[(int64_t)f * n_envs + e] = recs[e].w[w0 + f];
+}
+
+// vn_set_episode_returns / the schedule position: word w of every record = src[e] (or 0).
+__global__ void rec_scatter_kernel(EnvRec* recs, int n_envs, int w, const int32_t* src) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_envs) return;
+  recs[e].w[w] = src ? src[e] : 0;
+}
+
+// vn_set_state: the seven state words from the [7][E] table, then the cached neighbours and
+// scene fields that belong to the new (scene, state). A scene or state outside the tables
+// is kept as given but looked up clamped, so a bad table cannot make this kernel read past them.
+__global__ void set_state_kernel(EnvRec* recs, int n_envs, const int32_t* src, const SceneDev* scenes,
+                                 int n_scenes, const int32_t* graph) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_envs) return;
+  EnvRec* R = recs + e;
+  for (int f = 0; f < ST_COUNT; ++f) R->w[RW_ST + f] = src[(int64_t)f * n_envs + e];
+  const SceneDev S = scenes[min(max(src[(int64_t)ST_SCENE * n_envs + e], 0), n_scenes - 1)];
+  const int s = min(max(src[(int64_t)ST_STATE * n_envs + e], 0), S.n - 1);
+  *reinterpret_cast<i32x4*>(R->w + RW_NB) = *reinterpret_cast<const i32x4*>(graph + ((int64_t)S.graph_off + s) * 4);
+  store_scene_cache(R, scene_cache(S));
 }
 
 __global__ void synth_frames_kernel(uint8_t* arena, int64_t row_base, int n_rows, int64_t frame_bytes,
@@ -528,8 +671,7 @@ struct vn_ctx {
   int32_t* spd = nullptr;
   SceneDev* scenes = nullptr;
   std::vector<SceneDev> scenes_host;
-  int32_t* st = nullptr;
-  float* ep_ret = nullptr;
+  EnvRec* recs = nullptr;  // [n_envs] per-env records (state, return, cached fields, output record)
   int32_t* env_scene = nullptr;
   int32_t* tasks = nullptr;
   int n_tasks = 0;
@@ -548,9 +690,7 @@ struct vn_ctx {
   uint8_t* info_trunc = nullptr;
   int32_t* info_img_row = nullptr;
   int32_t* info_goal_row = nullptr;
-  // output reuse: the per-env records (device, stream-ordered) and the host switch
-  uint64_t* rec_addr = nullptr;
-  int32_t* rec_row = nullptr;
+  // output reuse: the host switch (what each env last wrote is in its record)
   int reuse = 0;       // vn_set_output_reuse
   int reuse_arm = 0;   // the next two-frame launch still writes every row
 };
@@ -576,8 +716,7 @@ EnvArgs make_args(vn_ctx* c) {
   a.spd = c->spd;
   a.arena = c->arena;
   a.frame_bytes = c->frame_bytes;
-  a.st = c->st;
-  a.ep_ret = c->ep_ret;
+  a.recs = c->recs;
   a.env_scene = c->env_scene;
   a.tasks = c->tasks;
   a.sched = c->sched;
@@ -598,8 +737,6 @@ EnvArgs make_args(vn_ctx* c) {
   a.info_trunc = c->info_trunc;
   a.info_img_row = c->info_img_row;
   a.info_goal_row = c->info_goal_row;
-  a.rec_addr = c->rec_addr;
-  a.rec_row = c->rec_row;
   return a;
 }
 
@@ -638,8 +775,8 @@ int launch_env(vn_ctx* c, const EnvArgs& a, hipStream_t stream) {
 
 void free_ctx(vn_ctx* c) {
   if (!c) return;
-  void* ptrs[] = {c->arena, c->graph, c->spd, c->scenes, c->st, c->ep_ret, c->env_scene,
-                  c->tasks, c->sched, c->flags, c->cur_order, c->cur_count, c->rec_addr, c->rec_row};
+  void* ptrs[] = {c->arena, c->graph, c->spd, c->scenes, c->recs, c->env_scene,
+                  c->tasks, c->sched, c->flags, c->cur_order, c->cur_count};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete c;
@@ -737,9 +874,8 @@ int vn_create(const vn_scene_desc* scenes, int n_scenes, int n_envs, uint64_t se
   };
   bool ok = alloc((void**)&c->arena, (size_t)(rows * F)) && alloc((void**)&c->graph, g32.size() * 4) &&
             alloc((void**)&c->spd, spd32.size() * 4) && alloc((void**)&c->scenes, sh.size() * sizeof(SceneDev)) &&
-            alloc((void**)&c->st, (size_t)ST_COUNT * n_envs * 4) && alloc((void**)&c->ep_ret, (size_t)n_envs * 4) &&
-            alloc((void**)&c->env_scene, (size_t)n_envs * 4) && alloc((void**)&c->flags, 4) &&
-            alloc((void**)&c->rec_addr, (size_t)2 * n_envs * 8) && alloc((void**)&c->rec_row, (size_t)2 * n_envs * 4);
+            alloc((void**)&c->recs, (size_t)n_envs * sizeof(EnvRec)) &&
+            alloc((void**)&c->env_scene, (size_t)n_envs * 4) && alloc((void**)&c->flags, 4);
   if (!ok) {
     free_ctx(c);
     return fail(VN_ENOMEM, "vn_create: device allocation failed");
@@ -751,12 +887,10 @@ int vn_create(const vn_scene_desc* scenes, int n_scenes, int n_envs, uint64_t se
   if (e == hipSuccess) e = hipMemcpy(c->spd, spd32.data(), spd32.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(c->scenes, sh.data(), sh.size() * sizeof(SceneDev), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(c->env_scene, es.data(), es.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(c->st, 0, (size_t)ST_COUNT * n_envs * 4);
-  if (e == hipSuccess) e = hipMemset(c->ep_ret, 0, (size_t)n_envs * 4);
+  // zero records: reset count and schedule position 0, and a null output address, which
+  // matches no destination (the first launch writes every row)
+  if (e == hipSuccess) e = hipMemset(c->recs, 0, (size_t)n_envs * sizeof(EnvRec));
   if (e == hipSuccess) e = hipMemset(c->flags, 0, 4);
-  // a null address matches no destination: the first launch writes every row
-  if (e == hipSuccess) e = hipMemset(c->rec_addr, 0, (size_t)2 * n_envs * 8);
-  if (e == hipSuccess) e = hipMemset(c->rec_row, 0, (size_t)2 * n_envs * 4);
   for (int k = 0; k < n_scenes && e == hipSuccess; ++k) {
     const vn_scene_desc& d = scenes[k];
     if (d.companion)
@@ -899,7 +1033,9 @@ int vn_set_schedule(vn_ctx* c, const int32_t* start_goal_dev, int len) {
     VN_HIP(hipMemcpy(c->sched, start_goal_dev, bytes, hipMemcpyDefault));
     c->sched_len = len;
   }
-  VN_HIP(hipMemset(c->st + (size_t)ST_SCHED * c->n_envs, 0, (size_t)c->n_envs * 4));
+  hipLaunchKernelGGL(rec_scatter_kernel, dim3((c->n_envs + 255) / 256), dim3(256), 0, 0, c->recs, c->n_envs,
+                     RW_ST + ST_SCHED, (const int32_t*)nullptr);
+  VN_HIP(hipGetLastError());
   return VN_OK;
 }
 
@@ -1039,28 +1175,36 @@ int vn_gather_rows(const uint8_t* src_dev, int64_t row_bytes, const int32_t* row
 int vn_get_state(vn_ctx* c, int32_t* dst, vn_stream_t stream) {
   if (!c || !dst) return fail(VN_EINVAL, "vn_get_state: NULL argument");
   DeviceGuard guard(c->device);
-  VN_HIP(hipMemcpyAsync(dst, c->st, (size_t)ST_COUNT * c->n_envs * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  hipLaunchKernelGGL(rec_gather_kernel, dim3((c->n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, c->recs,
+                     c->n_envs, RW_ST, ST_COUNT, dst);
+  VN_HIP(hipGetLastError());
   return VN_OK;
 }
 
 int vn_set_state(vn_ctx* c, const int32_t* src, vn_stream_t stream) {
   if (!c || !src) return fail(VN_EINVAL, "vn_set_state: NULL argument");
   DeviceGuard guard(c->device);
-  VN_HIP(hipMemcpyAsync(c->st, src, (size_t)ST_COUNT * c->n_envs * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  hipLaunchKernelGGL(set_state_kernel, dim3((c->n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, c->recs,
+                     c->n_envs, src, c->scenes, c->n_scenes, c->graph);
+  VN_HIP(hipGetLastError());
   return VN_OK;
 }
 
 int vn_get_episode_returns(vn_ctx* c, float* dst, vn_stream_t stream) {
   if (!c || !dst) return fail(VN_EINVAL, "vn_get_episode_returns: NULL argument");
   DeviceGuard guard(c->device);
-  VN_HIP(hipMemcpyAsync(dst, c->ep_ret, (size_t)c->n_envs * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  hipLaunchKernelGGL(rec_gather_kernel, dim3((c->n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, c->recs,
+                     c->n_envs, RW_RET, 1, reinterpret_cast<int32_t*>(dst));
+  VN_HIP(hipGetLastError());
   return VN_OK;
 }
 
 int vn_set_episode_returns(vn_ctx* c, const float* src, vn_stream_t stream) {
   if (!c || !src) return fail(VN_EINVAL, "vn_set_episode_returns: NULL argument");
   DeviceGuard guard(c->device);
-  VN_HIP(hipMemcpyAsync(c->ep_ret, src, (size_t)c->n_envs * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  hipLaunchKernelGGL(rec_scatter_kernel, dim3((c->n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, c->recs,
+                     c->n_envs, RW_RET, reinterpret_cast<const int32_t*>(src));
+  VN_HIP(hipGetLastError());
   return VN_OK;
 }
 

@@ -208,7 +208,10 @@ int vn_gather_rows(const uint8_t* src_dev, int64_t row_bytes, const int32_t* row
                    vn_stream_t stream);
 
 /* Per-env state tensors (device, [n_envs] int32 each): for checkpoint/resume and tests.
- * Order: scene, state, goal, obs_state, elapsed, episode(reset count), sched_pos. */
+ * Order: scene, state, goal, obs_state, elapsed, episode(reset count), sched_pos.
+ * Both are small stream-ordered kernels over the context's per-env records; vn_set_state
+ * also rebuilds what a record caches for its (scene, state): graph neighbours, row bases,
+ * rewards. Scene and state must be inside the tables vn_create was given. */
 int vn_get_state(vn_ctx* ctx, int32_t* dst_dev_7xE, vn_stream_t stream);
 int vn_set_state(vn_ctx* ctx, const int32_t* src_dev_7xE, vn_stream_t stream);
 /* Running (unfinished) episode return per env, [n_envs] f32 on the device: the rest of the
