@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "vn_common.h"
+#include "vn_unit_float.h"
 
 namespace vn {
 
@@ -76,7 +77,8 @@ enum {
   RW_R_STEP = 16,
   RW_R_COLL = 17,
   RW_OUT_ROW = 18,    // [2] arena row last written to the image / goal output row
-  RW_OUT_ADDR = 20,   // [2] x 64 bit: that output row's address (0 matches nothing)
+  RW_OUT_ADDR = 20,   // [2] x 64 bit: that output row's address (0 matches nothing); bit 63
+                      // (kOutF32) set when the row was written as f32 planes, not u8 HWC
   RW_USED = 24,
   RW_WORDS = 32,
 };
@@ -84,6 +86,9 @@ struct alignas(128) EnvRec {
   int32_t w[RW_WORDS];
 };
 static_assert(sizeof(EnvRec) == 128, "one record per 128-B line");
+// A u8 row and an f32 row at one address are different contents: the record tells them apart
+// on the device, so replayed graphs and interleaved vn_step / vn_step_f32 calls stay correct.
+constexpr uint64_t kOutF32 = 1ull << 63;
 
 typedef int32_t i32x16 __attribute__((ext_vector_type(16), may_alias, aligned(64)));
 typedef int32_t i32x8 __attribute__((ext_vector_type(8), may_alias, aligned(32)));
@@ -140,11 +145,18 @@ struct EnvArgs {
   // output reuse (DESIGN.md "vn_step: output reuse"): whether this launch may skip a frame
   // whose destination row already holds it (the record's RW_OUT_* words say what it holds)
   int reuse;
+  // float observations (FMT_F32 instantiations only): pixels per frame (H W) and channels;
+  // obs / goal_out then point at float [n_envs][C][H][W]
+  int px, ch;
 };
 
 // MODE_STEP_HEADS: a step of vn_step_a2c that also computes the policy heads (its own
 // instantiation, so the plain step keeps its register budget)
 enum { MODE_STEP = 0, MODE_RESET = 1, MODE_OBSERVE = 2, MODE_STEP_HEADS = 3 };
+// The frame tail's output format: u8 HWC rows (VEC = 16 / 4 / 1 bytes per lane), or f32 CHW
+// rows (VEC = 16: the 4-pixel lanes of cvt_two_frames, VEC = 4: cvt_frames_scalar). Own
+// instantiations, so the u8 kernels are the code they were.
+enum { FMT_U8 = 0, FMT_F32 = 1 };
 constexpr int kEnvsPerBlock = 4;
 constexpr int kStartRounds = 16;  // 1024 rejection attempts before flagging
 
@@ -352,6 +364,152 @@ __device__ __forceinline__ void copy_one_frame(uint8_t* __restrict__ d, const ui
   }
 }
 
+// Float observations (vn_step_f32 / vn_observe_f32; DESIGN.md "vn_step: float observations"):
+// the u8 HWC arena row leaves as three f32 planes [3][H][W] of float(u8) / 255
+// (unit_from_byte_value: the division's bits). A lane owns 4 consecutive pixels, group q:
+// one 12-B load at byte 12 q (a wave instruction reads 768 contiguous bytes), 12
+// conversions, and one 16-B nt store per plane at float 4 q (a wave instruction writes 1024
+// contiguous bytes of a plane), so nothing is staged in LDS and no line is stored in parts.
+// Needs P = H W a multiple of 4 and 16-B aligned planes; anything else takes cvt_frames_scalar.
+typedef uint32_t u32x3 __attribute__((ext_vector_type(3), may_alias, aligned(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4), may_alias, aligned(16)));
+
+__device__ __forceinline__ u32x3 ld12(const uint8_t* __restrict__ s, int q) {
+  return *reinterpret_cast<const u32x3*>(s + 12 * q);
+}
+template <int K>
+__device__ __forceinline__ float unit_byte(uint32_t w) {
+  return unit_from_byte_value((float)((w >> (8 * K)) & 0xffu));  // v_cvt_f32_ubyteK
+}
+// bytes r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3 of pixels 4 q .. 4 q + 3
+__device__ __forceinline__ void cvt_store12(float* __restrict__ d, int P, int q, const u32x3 w) {
+  // one plane's 4 floats are converted and stored at a time (the scheduling barriers): left
+  // to itself the scheduler converts a whole trip before its first store (132 VGPRs, 3 waves
+  // per SIMD), and with a barrier per group only it still needs 84
+  __builtin_amdgcn_sched_barrier(0);
+  const f32x4 pr = {unit_byte<0>(w.x), unit_byte<3>(w.x), unit_byte<2>(w.y), unit_byte<1>(w.z)};
+  __builtin_nontemporal_store(pr, reinterpret_cast<f32x4*>(d + 4 * q));
+  __builtin_amdgcn_sched_barrier(0);
+  const f32x4 pg = {unit_byte<1>(w.x), unit_byte<0>(w.y), unit_byte<3>(w.y), unit_byte<2>(w.z)};
+  __builtin_nontemporal_store(pg, reinterpret_cast<f32x4*>(d + P + 4 * q));
+  __builtin_amdgcn_sched_barrier(0);
+  const f32x4 pb = {unit_byte<2>(w.x), unit_byte<1>(w.y), unit_byte<0>(w.z), unit_byte<3>(w.z)};
+  __builtin_nontemporal_store(pb, reinterpret_cast<f32x4*>(d + 2 * P + 4 * q));
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// Both frames of one env: 4 + 4 loads of 12 B in flight per lane, a trip is 256 groups
+// (1024 pixels) of each frame. The structure is copy_two_frames': a first trip with a fixed
+// load count around mid(), wave-uniform full trips, and a remainder (84 x 84 = 1764 groups =
+// 6 trips + 228) whose predicated loads are all issued before its stores.
+template <class Mid>
+__device__ __forceinline__ void cvt_two_frames(float* __restrict__ d1, const uint8_t* __restrict__ s1,
+                                               float* __restrict__ d2, const uint8_t* __restrict__ s2, int P,
+                                               int lane, Mid mid) {
+  constexpr int U = 4;
+  const int n = P >> 2;
+  int base = 0;
+  {  // first trip, mid() inside it: always U loads per stream (see copy_two_frames)
+    const bool full = 64 * U <= n;  // wave-uniform
+    const int i0 = full ? lane : min(lane, n - 1), step = full ? 64 : 0;
+    u32x3 va[U], vb[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) va[u] = ld12(s1, i0 + step * u);
+#pragma unroll
+    for (int u = 0; u < U; ++u) vb[u] = ld12(s2, i0 + step * u);
+    mid();
+    if (full) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) cvt_store12(d1, P, lane + 64 * u, va[u]);
+#pragma unroll
+      for (int u = 0; u < U; ++u) cvt_store12(d2, P, lane + 64 * u, vb[u]);
+      base = 64 * U;
+    }
+  }
+  for (; base + 64 * U <= n; base += 64 * U) {
+    const int i = base + lane;
+    u32x3 va[U], vb[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) va[u] = ld12(s1, i + 64 * u);
+#pragma unroll
+    for (int u = 0; u < U; ++u) vb[u] = ld12(s2, i + 64 * u);
+#pragma unroll
+    for (int u = 0; u < U; ++u) cvt_store12(d1, P, i + 64 * u, va[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u) cvt_store12(d2, P, i + 64 * u, vb[u]);
+  }
+  if (base < n) {
+    const int i = base + lane;
+    u32x3 va[U] = {}, vb[U] = {};
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (i + 64 * u < n) va[u] = ld12(s1, i + 64 * u);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (i + 64 * u < n) vb[u] = ld12(s2, i + 64 * u);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (i + 64 * u < n) cvt_store12(d1, P, i + 64 * u, va[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (i + 64 * u < n) cvt_store12(d2, P, i + 64 * u, vb[u]);
+  }
+}
+
+// One frame (the other one of the env is already in its output row): the same 8 loads in
+// flight on one stream, a trip is 512 groups (2048 pixels); 84 x 84 = 3 trips + 228.
+template <class Mid>
+__device__ __forceinline__ void cvt_one_frame(float* __restrict__ d, const uint8_t* __restrict__ s, int P, int lane,
+                                              Mid mid) {
+  constexpr int U = 8;
+  const int n = P >> 2;
+  int base = 0;
+  {  // first trip, mid() inside it: always U loads
+    const bool full = 64 * U <= n;  // wave-uniform
+    const int i0 = full ? lane : min(lane, n - 1), step = full ? 64 : 0;
+    u32x3 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = ld12(s, i0 + step * u);
+    mid();
+    if (full) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) cvt_store12(d, P, lane + 64 * u, v[u]);
+      base = 64 * U;
+    }
+  }
+  for (; base + 64 * U <= n; base += 64 * U) {
+    const int i = base + lane;
+    u32x3 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = ld12(s, i + 64 * u);
+#pragma unroll
+    for (int u = 0; u < U; ++u) cvt_store12(d, P, i + 64 * u, v[u]);
+  }
+  if (base < n) {
+    const int i = base + lane;
+    u32x3 v[U] = {};
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (i + 64 * u < n) v[u] = ld12(s, i + 64 * u);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (i + 64 * u < n) cvt_store12(d, P, i + 64 * u, v[u]);
+  }
+}
+
+// The fallback (P % 4 != 0, channels != 3 or planes that are only 4-B aligned): one element
+// per lane and trip, plane by plane. d2 / s2 may be NULL (one frame).
+__device__ __forceinline__ void cvt_frames_scalar(float* __restrict__ d1, const uint8_t* __restrict__ s1,
+                                                  float* __restrict__ d2, const uint8_t* __restrict__ s2, int P,
+                                                  int C, int lane) {
+  for (int c = 0; c < C; ++c) {
+    for (int p = lane; p < P; p += 64) {
+      d1[(int64_t)c * P + p] = unit_from_u8(s1[(int64_t)p * C + c]);
+      if (d2) d2[(int64_t)c * P + p] = unit_from_u8(s2[(int64_t)p * C + c]);
+    }
+  }
+}
+
 // The scene fields a record caches (a reset or vn_set_state may change the env's scene).
 struct SceneCache {
   int32_t row_base, comp_base;
@@ -373,7 +531,7 @@ __device__ __forceinline__ void store_out_record(EnvRec* R, int32_t row1, int32_
       i32x4{(int32_t)(uint32_t)a1, (int32_t)(uint32_t)(a1 >> 32), (int32_t)(uint32_t)a2, (int32_t)(uint32_t)(a2 >> 32)};
 }
 
-template <int MODE, int VEC>
+template <int MODE, int VEC, int FMT = FMT_U8>
 __global__ __launch_bounds__(256) void env_kernel(EnvArgs a) {
   const int lane = threadIdx.x & 63;
   const int e = uni(blockIdx.x * kEnvsPerBlock + (threadIdx.x >> 6));
@@ -555,7 +713,52 @@ __global__ __launch_bounds__(256) void env_kernel(EnvArgs a) {
     emit(false, 0, 0, 0, 0);
     return;
   }
-  if (a.obs != nullptr && a.goal_out != nullptr) {
+  if constexpr (FMT == FMT_F32) {
+    // the float tail: the rows of the u8 tail below, F floats each, addresses recorded with
+    // kOutF32 (a u8 record never matches here, nor a float record there)
+    const int64_t F = a.frame_bytes;
+    const int P = a.px;
+    float* o1 = reinterpret_cast<float*>(a.obs);
+    float* o2 = reinterpret_cast<float*>(a.goal_out);
+    if (o1 != nullptr && o2 != nullptr) {
+      float* d1 = o1 + (int64_t)e * F;
+      float* d2 = o2 + (int64_t)e * F;
+      const uint64_t t1 = (uint64_t)d1 | kOutF32, t2 = (uint64_t)d2 | kOutF32;
+      const bool keep1 = a.reuse && rec_a1 == t1 && rec_r1 == img_row;
+      const bool keep2 = a.reuse && rec_a2 == t2 && rec_r2 == goal_row;
+      auto mid = [&]() __attribute__((always_inline)) { emit(true, img_row, goal_row, t1, t2); };
+      const uint8_t* s1 = a.arena + (int64_t)img_row * F;
+      const uint8_t* s2 = a.arena + (int64_t)goal_row * F;
+      if (keep1 && keep2) {
+        mid();
+      } else if constexpr (VEC == 16) {
+        if (!keep1 && !keep2)
+          cvt_two_frames(d1, s1, d2, s2, P, lane, mid);
+        else
+          cvt_one_frame(keep1 ? d2 : d1, keep1 ? s2 : s1, P, lane, mid);
+      } else {
+        mid();
+        if (!keep1 && !keep2)
+          cvt_frames_scalar(d1, s1, d2, s2, P, a.ch, lane);
+        else
+          cvt_frames_scalar(keep1 ? d2 : d1, keep1 ? s2 : s1, nullptr, nullptr, P, a.ch, lane);
+      }
+    } else if (o1 != nullptr || o2 != nullptr) {
+      const int k = o1 ? 0 : 1;  // which frame: always converted, its record updated
+      float* d = (k == 0 ? o1 : o2) + (int64_t)e * F;
+      const uint8_t* src = a.arena + (int64_t)(k == 0 ? img_row : goal_row) * F;
+      // the other frame's record no longer holds if this row was its destination (either format)
+      const uint64_t oa = k == 0 ? rec_a2 : rec_a1;
+      const uint64_t other = (oa & ~kOutF32) == (uint64_t)d ? 0 : oa;
+      if (k == 0)
+        emit(true, img_row, rec_r2, (uint64_t)d | kOutF32, other);
+      else
+        emit(true, rec_r1, goal_row, other, (uint64_t)d | kOutF32);
+      cvt_frames_scalar(d, src, nullptr, nullptr, P, a.ch, lane);
+    } else {
+      emit(false, 0, 0, 0, 0);
+    }
+  } else if (a.obs != nullptr && a.goal_out != nullptr) {
     const int64_t F = a.frame_bytes;
     uint8_t* d1 = a.obs + (int64_t)e * F;
     uint8_t* d2 = a.goal_out + (int64_t)e * F;
@@ -666,6 +869,7 @@ struct vn_ctx {
   int n_envs = 0, n_scenes = 0;
   uint64_t seed = 0;
   int64_t frame_bytes = 0, n_rows = 0;
+  int px = 0, channels = 0;  // frame_bytes = px * channels
   uint8_t* arena = nullptr;
   int32_t* graph = nullptr;
   int32_t* spd = nullptr;
@@ -737,6 +941,8 @@ EnvArgs make_args(vn_ctx* c) {
   a.info_trunc = c->info_trunc;
   a.info_img_row = c->info_img_row;
   a.info_goal_row = c->info_goal_row;
+  a.px = c->px;
+  a.ch = c->channels;
   return a;
 }
 
@@ -745,7 +951,7 @@ EnvArgs make_args(vn_ctx* c) {
 // write. A launch that is only being captured into a graph has not run yet (and may never):
 // while armed it is recorded as a full write and leaves the arm for the next eager launch.
 // A one-frame launch copies unconditionally and leaves the arm for the next two-frame one.
-int take_reuse(vn_ctx* c, const uint8_t* obs, const uint8_t* goal, hipStream_t stream) {
+int take_reuse(vn_ctx* c, const void* obs, const void* goal, hipStream_t stream) {
   if (!obs || !goal || !c->reuse) return 0;
   if (!c->reuse_arm) return 1;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -769,6 +975,20 @@ int launch_env(vn_ctx* c, const EnvArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL((env_kernel<MODE, 4>), grid, block, 0, stream, a);
   else
     hipLaunchKernelGGL((env_kernel<MODE, 1>), grid, block, 0, stream, a);
+  VN_HIP(hipGetLastError());
+  return VN_OK;
+}
+
+// The float tail: 4-pixel lanes when the frame is 3 channels of a multiple of 4 pixels and
+// both rows' planes are 16-B aligned (every plane then is: F and P floats are multiples of 16 B).
+template <int MODE>
+int launch_env_f32(vn_ctx* c, const EnvArgs& a, hipStream_t stream) {
+  const dim3 grid((c->n_envs + kEnvsPerBlock - 1) / kEnvsPerBlock), block(64 * kEnvsPerBlock);
+  const bool vec = c->channels == 3 && c->px % 4 == 0 && (uintptr_t)a.obs % 16 == 0 && (uintptr_t)a.goal_out % 16 == 0;
+  if (vec)
+    hipLaunchKernelGGL((env_kernel<MODE, 16, FMT_F32>), grid, block, 0, stream, a);
+  else
+    hipLaunchKernelGGL((env_kernel<MODE, 4, FMT_F32>), grid, block, 0, stream, a);
   VN_HIP(hipGetLastError());
   return VN_OK;
 }
@@ -806,6 +1026,7 @@ int vn_create(const vn_scene_desc* scenes, int n_scenes, int n_envs, uint64_t se
   const int H = scenes[0].height, W = scenes[0].width, C = scenes[0].channels;
   if (H <= 0 || W <= 0 || C <= 0) return fail(VN_EINVAL, "vn_create: bad frame shape");
   const int64_t F = (int64_t)H * W * C;
+  if (F >= (1ll << 31)) return fail(VN_EINVAL, "vn_create: frames of 2^31 bytes or more");
   int64_t rows = 0, graph_rows = 0, spd_elems = 0;
   std::vector<SceneDev> sh(n_scenes);
   for (int k = 0; k < n_scenes; ++k) {
@@ -866,6 +1087,8 @@ int vn_create(const vn_scene_desc* scenes, int n_scenes, int n_envs, uint64_t se
   c->n_scenes = n_scenes;
   c->seed = seed;
   c->frame_bytes = F;
+  c->px = H * W;
+  c->channels = C;
   c->n_rows = rows;
   c->scenes_host = sh;
   c->spd_host = spd32;
@@ -966,6 +1189,37 @@ int vn_step(vn_ctx* c, const int32_t* actions_dev, uint8_t* obs_dev, uint8_t* go
   a.state_out = state_dev;
   a.reuse = take_reuse(c, obs_dev, goal_dev, (hipStream_t)stream);
   return launch_env<MODE_STEP>(c, a, (hipStream_t)stream);
+}
+
+int vn_observe_f32(vn_ctx* c, float* obs_chw_dev, float* goal_chw_dev, int32_t* state_dev, vn_stream_t stream) {
+  if (!c) return fail(VN_EINVAL, "vn_observe_f32: NULL ctx");
+  if (((uintptr_t)obs_chw_dev | (uintptr_t)goal_chw_dev) & 3)
+    return fail(VN_EINVAL, "vn_observe_f32: float outputs must be 4-byte aligned");
+  DeviceGuard guard(c->device);
+  EnvArgs a = make_args(c);
+  a.obs = reinterpret_cast<uint8_t*>(obs_chw_dev);
+  a.goal_out = reinterpret_cast<uint8_t*>(goal_chw_dev);
+  a.state_out = state_dev;
+  a.reuse = take_reuse(c, obs_chw_dev, goal_chw_dev, (hipStream_t)stream);
+  return launch_env_f32<MODE_OBSERVE>(c, a, (hipStream_t)stream);
+}
+
+int vn_step_f32(vn_ctx* c, const int32_t* actions_dev, float* obs_chw_dev, float* goal_chw_dev, float* reward_dev,
+                uint8_t* done_dev, int32_t* state_dev, vn_stream_t stream) {
+  if (!c) return fail(VN_EINVAL, "vn_step_f32: NULL ctx");
+  if (!actions_dev) return fail(VN_EINVAL, "vn_step_f32: actions is NULL");
+  if (((uintptr_t)obs_chw_dev | (uintptr_t)goal_chw_dev) & 3)
+    return fail(VN_EINVAL, "vn_step_f32: float outputs must be 4-byte aligned");
+  DeviceGuard guard(c->device);
+  EnvArgs a = make_args(c);
+  a.actions = actions_dev;
+  a.obs = reinterpret_cast<uint8_t*>(obs_chw_dev);
+  a.goal_out = reinterpret_cast<uint8_t*>(goal_chw_dev);
+  a.reward = reward_dev;
+  a.done = done_dev;
+  a.state_out = state_dev;
+  a.reuse = take_reuse(c, obs_chw_dev, goal_chw_dev, (hipStream_t)stream);
+  return launch_env_f32<MODE_STEP>(c, a, (hipStream_t)stream);
 }
 
 int vn_step_a2c(vn_ctx* c, const vn_a2c_step* p, float* reward_dev, uint8_t* done_dev, int32_t* state_dev,

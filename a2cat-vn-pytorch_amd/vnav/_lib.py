@@ -100,6 +100,8 @@ SIGNATURES = {
     "vn_reset": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vn_observe": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vn_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vn_observe_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vn_step_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vn_set_info_buffers": (c_int, [c_void_p] + [c_void_p] * 6),
     "vn_set_schedule": (c_int, [c_void_p, c_void_p, c_int]),
     "vn_set_tasks": (c_int, [c_void_p, P(c_int32), c_int]),

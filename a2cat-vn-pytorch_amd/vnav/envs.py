@@ -8,8 +8,11 @@ with baselines-style auto-reset, ``call_unwrapped('set_complexity', x)`` and
 
 Observations are the tuple ``(image, goal)`` of uint8 ``[E,H,W,C]`` device tensors (the
 raw cached frames, cached.py:59-60 / gym_thor_cached.py:52-53). The reference
-wrapper chain TransposeImage + ScaledFloatFrame is ``to_float_chw`` below; the policy
-kernels consume the uint8 frames directly and fuse that conversion.
+wrapper chain TransposeImage + ScaledFloatFrame is ``obs_format="f32_chw"``: the step
+itself then emits float32 ``[E,C,H,W]`` in [0, 1] (``vn_step_f32``), with the wrappers'
+arithmetic bit for bit. ``to_float_chw`` below is the same chain in torch, for frames that
+are already out of the env; the policy kernels consume the uint8 frames directly and fuse
+that conversion.
 """
 import ctypes
 
@@ -19,6 +22,7 @@ import torch
 from . import _lib
 from .scenes import Scene
 
+OBS_FORMATS = ("u8_hwc", "f32_chw")
 ST_FIELDS = ("scene", "state", "goal", "obs_state", "elapsed", "episode", "sched_pos")
 
 
@@ -31,7 +35,16 @@ class VectorEnv:
     num_actions = 4  # THORDiscreteCachedEnv.get_action_size (cached.py:66-68)
 
     def __init__(self, scenes, num_envs, seed=0, device=None, max_episode_steps=900, tasks=None,
-                 env_scenes=None, autoreset=True, aux_observations=False, reuse_outputs=True):
+                 env_scenes=None, autoreset=True, aux_observations=False, reuse_outputs=True,
+                 obs_format="u8_hwc"):
+        """obs_format: "u8_hwc" (default) returns and takes uint8 [E,H,W,C] frames; "f32_chw"
+        returns and takes float32 [E,C,H,W] frames in [0, 1], every value float(u8) / 255 as
+        fp32 division (ScaledFloatFrame's), converted in the step's own launch with the same
+        ``out=`` fast path and reuse contract. The extra depth / segmentation frames of
+        ``aux_observations=True`` stay uint8 [E,H,W,C] in either format. ``obs_shape`` is the
+        shape of one returned frame."""
+        if obs_format not in OBS_FORMATS:
+            raise ValueError("obs_format must be one of %s, got %r" % (OBS_FORMATS, obs_format))
         if isinstance(scenes, Scene):
             scenes = [scenes]
         if not scenes:
@@ -45,6 +58,15 @@ class VectorEnv:
         self.num_envs = int(num_envs)
         self.seed = int(seed)
         self.frame_shape = tuple(self.scenes[0].frame_shape)
+        self.obs_format = obs_format
+        if obs_format == "f32_chw":
+            self.obs_shape = (self.frame_shape[2],) + self.frame_shape[:2]
+            self._obs_dtype = torch.float32
+            self._vn_step, self._vn_observe = self.lib.vn_step_f32, self.lib.vn_observe_f32
+        else:
+            self.obs_shape = self.frame_shape
+            self._obs_dtype = torch.uint8
+            self._vn_step, self._vn_observe = self.lib.vn_step, self.lib.vn_observe
         descs = (_lib.SceneDesc * len(self.scenes))()
         self._keep = []
         for i, s in enumerate(self.scenes):
@@ -214,13 +236,13 @@ class VectorEnv:
 
     def _check_frames_out(self, img, goal):
         F = int(np.prod(self.frame_shape))
-        self._check_out("image", img, torch.uint8, self.num_envs * F)
-        self._check_out("goal", goal, torch.uint8, self.num_envs * F)
+        self._check_out("image", img, self._obs_dtype, self.num_envs * F)
+        self._check_out("goal", goal, self._obs_dtype, self.num_envs * F)
 
     def _frames(self):
-        shape = (self.num_envs,) + self.frame_shape
-        return (torch.empty(shape, dtype=torch.uint8, device=self.device),
-                torch.empty(shape, dtype=torch.uint8, device=self.device))
+        shape = (self.num_envs,) + self.obs_shape
+        return (torch.empty(shape, dtype=self._obs_dtype, device=self.device),
+                torch.empty(shape, dtype=self._obs_dtype, device=self.device))
 
     def _arm_reuse(self):
         """The caller's own buffers were (re)validated: the next launch writes every row, later
@@ -249,9 +271,10 @@ class VectorEnv:
         return self.observe()
 
     def observe(self, out=None, gather=True):
-        """Current (image, goal) frames; gather=False only refreshes info img_row/goal_row."""
+        """Current (image, goal) frames in the env's obs_format; gather=False only refreshes
+        info img_row/goal_row."""
         if not gather:
-            _lib.check(self.lib.vn_observe(self._ctx, None, None, None, self._stream()), "vn_observe")
+            _lib.check(self._vn_observe(self._ctx, None, None, None, self._stream()), "vn_observe")
             return None, None
         img, goal = out if out is not None else self._frames()
         self._check_frames_out(img, goal)
@@ -259,14 +282,16 @@ class VectorEnv:
             self._disarm_reuse()
         else:
             self._arm_reuse()
-        _lib.check(self.lib.vn_observe(self._ctx, _lib.ptr(img), _lib.ptr(goal), None, self._stream()), "vn_observe")
+        _lib.check(self._vn_observe(self._ctx, _lib.ptr(img), _lib.ptr(goal), None, self._stream()), "vn_observe")
         if self.aux_observations:
             return (img, goal) + self._gather_aux()
         return img, goal
 
     def step(self, actions, out=None, gather=True):
         """actions: int32 [E] device tensor (other integer dtypes are converted).
-        Returns ((image, goal), reward f32 [E], done bool [E], info dict of [E] tensors).
+        Returns ((image, goal), reward f32 [E], done bool [E], info dict of [E] tensors); the
+        frames are uint8 [E,H,W,C], or float32 [E,C,H,W] with ``obs_format="f32_chw"`` (the
+        ``out`` image / goal buffers then are float32 too).
         Without ``out`` every returned tensor is fresh, info included (a caller may keep step
         t's results while stepping on). ``out`` = dict of preallocated outputs (image, goal,
         reward, done, state) to write in place: the fast path, where nothing is allocated or
@@ -299,7 +324,7 @@ class VectorEnv:
             if c is not None and all(x is y for x, y in zip(bufs, c[0])) and \
                     c[2] == tuple((t.data_ptr(), t.numel()) if t is not None else None for t in bufs):
                 P = c[1]
-                _lib.check(self.lib.vn_step(self._ctx, _lib.ptr(a), P[0], P[1], P[2], P[3], P[4], self._stream()),
+                _lib.check(self._vn_step(self._ctx, _lib.ptr(a), P[0], P[1], P[2], P[3], P[4], self._stream()),
                            "vn_step")
                 info = dict(self._info)
                 info["state"] = bufs[4]
@@ -325,8 +350,8 @@ class VectorEnv:
                 self._out_cache = (bufs, tuple(_lib.ptr(t) for t in bufs),
                                    tuple((t.data_ptr(), t.numel()) if t is not None else None for t in bufs))
                 self._arm_reuse()
-        _lib.check(self.lib.vn_step(self._ctx, _lib.ptr(a), _lib.ptr(img), _lib.ptr(goal), _lib.ptr(reward),
-                                    _lib.ptr(done), _lib.ptr(state), self._stream()), "vn_step")
+        _lib.check(self._vn_step(self._ctx, _lib.ptr(a), _lib.ptr(img), _lib.ptr(goal), _lib.ptr(reward),
+                                 _lib.ptr(done), _lib.ptr(state), self._stream()), "vn_step")
         # fresh info tensors unless the caller chose the in-place path (out=...)
         info = {k: v.clone() for k, v in self._info.items()} if out is None else dict(self._info)
         info["state"] = state

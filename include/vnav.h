@@ -25,6 +25,8 @@
  *                            (experiments/thor_cached_auxiliary.py:66-67) and gym's
  *                            TimeLimit(max_episode_steps=900)
  *                            (environments/gym_ai2thor/__init__.py:45-49)
+ *   vn_step_f32 / vn_observe_f32 <- the same under the wrappers TransposeImage +
+ *                            ScaledFloatFrame (experiments/thor_cached_auxiliary.py:59-64)
  *   vn_policy_*           <- BigGoalHouseModel trunk + heads (models/goal.py:36-59,77-92)
  *   vn_a2c_*              <- the deep_rl A2C update used by the Trainer
  *                            (experiments/thor_cached_auxiliary.py:26-42)
@@ -106,6 +108,23 @@ int vn_observe(vn_ctx* ctx, uint8_t* obs_dev, uint8_t* goal_dev, int32_t* state_
  * done u8, state int32 (after any auto-reset). */
 int vn_step(vn_ctx* ctx, const int32_t* actions_dev, uint8_t* obs_dev, uint8_t* goal_dev,
             float* reward_dev, uint8_t* done_dev, int32_t* state_dev, vn_stream_t stream);
+
+/* vn_step / vn_observe with the frames as a PyTorch policy takes them: float32
+ * [n_envs][C][H][W] in [0, 1], the reference's TransposeImage + ScaledFloatFrame wrappers
+ * (experiments/thor_cached_auxiliary.py:59-64) done while the frame leaves the scene cache.
+ * Every value is float(u8) / 255.0f as IEEE fp32 division, bit for bit (ScaledFloatFrame's
+ * np.float32(u8) / 255.0; a multiplication by 1/255 is not). Everything else is vn_step's /
+ * vn_observe's: either frame pointer NULL (that frame is not written, the other one always
+ * is), both NULL (index-only), companion frames as the second output, the info buffers, and
+ * output reuse (vn_set_output_reuse: the same contract, for the float rows). The per-env
+ * record also holds the format of what it wrote, so u8 and f32 calls may be mixed, into the
+ * same memory too: a row written in one format is never taken for the other. The pointers
+ * must be 4-byte aligned; rows whose planes are 16-byte aligned, of 3-channel frames with
+ * H W a multiple of 4, take the vector path (16-byte stores). */
+int vn_observe_f32(vn_ctx* ctx, float* obs_chw_dev, float* goal_chw_dev, int32_t* state_dev,
+                   vn_stream_t stream);
+int vn_step_f32(vn_ctx* ctx, const int32_t* actions_dev, float* obs_chw_dev, float* goal_chw_dev,
+                float* reward_dev, uint8_t* done_dev, int32_t* state_dev, vn_stream_t stream);
 
 /* The A2C rollout's env step (the trainer's fast path; vn_step stays the gym/VecEnv
  * boundary): the action of env e is sampled in the step from the policy's output row e
