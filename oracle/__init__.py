@@ -25,4 +25,7 @@ Modules
               store's views and ReLU masks, gradients vs the fp64 oracle, the recurrent core
               vs torch's float64 nn.LSTM
   few_env_cases.py  case tables and inputs of the few-env / float-frame / 1..7-action tests
+  unreal_head_cases.py  case tables of the UNREAL head tests and the launch rules (split-K,
+              weight-gradient slabs, reduce lanes, colsum blocks) that place them
+  update_checks.py  one A2CTrainer update restated in float64, the UNREAL terms included
 """

@@ -31,7 +31,7 @@ import torch
 
 from oracle import a2c as oa2c
 from oracle.policy import AuxHeadsOracle, GoalNetOracle, aux_targets, frames_to_float
-from oracle.trunk_checks import (AUX_NAMES, NAMES, _check_masks_are_signs, _check_outputs, _elementwise, _err,
+from oracle.trunk_checks import (AUX_NAMES, NAMES, _check_masks_are_signs, _check_outputs, _err,
                                  _gpu_masks, _grads_vs_oracle, lstm_core_check)
 from oracle.trunk_checks import a2c_loss_grad as _loss_grad
 
@@ -204,123 +204,15 @@ def test_logged_run_shape_trainer_update_vs_fp64_oracle():
     draw on the rollout's logits, the rollout's logits / values against the masked fp64
     network, and the update's total gradient (A2C + 0.1 x deconv loss through BPTT) against
     the fp64 gradient."""
-    import dataclasses
-    import vnav
-    from oracle import envs as oe
-    from oracle import graph as og
-    from oracle import philox
-    from vnav import dist as vdist
-    from vnav.policy import frames_from_rows
-    maze = np.random.RandomState(2).rand(5, 6) > 0.2
-    graph, spd, _ = og.h5_tables(maze)
-    ns = len(graph)
-    rng = np.random.RandomState(4)
-    frames = rng.randint(0, 256, size=(ns, 174, 174, 3)).astype(np.uint8)
-    scene = vnav.scene_from_arrays(graph, spd, frames)
-    scene = dataclasses.replace(scene, depth=rng.randint(0, 256, size=(ns, 174, 174, 1)).astype(np.uint8),
-                                segmentation=rng.randint(0, 256, size=(ns, 174, 174, 3)).astype(np.uint8))
-    T, E, A, seed, env_seed, w = 20, 4, 4, 3, 11, 0.1
-    env = vnav.VectorEnv([scene], E, seed=env_seed, max_episode_steps=25)
-    tr = vnav.A2CTrainer(env, num_steps=T, seed=seed, max_time_steps=1e6, recurrent=True, aux_weight=w)
-    o = oe.VectorEnvOracle([dict(graph=graph, spd=spd, rewards=scene.rewards)], E, env_seed, max_steps=25)
-    tr.step(sync=True)
-    a1 = tr.actions.cpu().numpy().reshape(T, E)
-    for t in range(T):
-        o.step(a1[t])
-    h0, c0 = tr.h0.cpu().double(), tr.c0.cpu().double()
-    p0 = tr.params.detach().clone()
-    tr.rollout()
-    net = tr.net
-    N = T * E
-    masks = _gpu_masks(net, tr.acts, N)
-    bmasks = _gpu_masks(net, tr.boot_acts, E)
-    # the aux heads' ReLU masks: the same first layer run on the rollout's X4
-    a1buf, predbuf = net.aux_buffers(N)
-    net.aux_forward(tr.params, tr.acts, N, N, a1buf, predbuf, torch.empty(net.aux_workspace_floats(), device="cuda"))
-    amasks = [(a1buf[..., 16 * h:16 * h + 16] > 0).permute(0, 3, 1, 2).double().cpu() for h in range(3)]
-    rows_i, rows_g = tr.rows_img.cpu().numpy(), tr.rows_goal.cpu().numpy()
-    brows = (env._info["img_row"].cpu().numpy(), env._info["goal_row"].cpu().numpy())
-    actions = tr.actions.cpu().long()
-    rewards, dones = tr.rewards.cpu(), tr.dones.cpu()
-    out = tr.out.cpu().double()
-    boot = tr.boot_out.cpu().double()
-    lmask, lra = tr.masks.cpu().double(), tr.lra.cpu().double()
-    bmask, blra = tr.boot_mask.cpu().double(), tr.boot_lra.cpu().double()
-    tr.update()
-    grads = tr.grads.clone()
-    torch.cuda.synchronize()
-
-    # env transitions (index-only vn_step) vs the env oracle on the same actions
-    a2 = actions.numpy().reshape(T, E)
-    for t in range(T):
-        r = o.step(a2[t])
-        ri = rows_i[(t + 1) * E:(t + 2) * E] if t + 1 < T else brows[0]
-        rg = rows_g[(t + 1) * E:(t + 2) * E] if t + 1 < T else brows[1]
-        assert np.array_equal(ri, r["img_row"]) and np.array_equal(rg, r["goal_row"]), t
-        assert np.array_equal(rewards[t].numpy().view(np.uint32), r["reward"].view(np.uint32)), t
-        assert np.array_equal(dones[t].numpy(), r["done"]), t
-    # sampled actions: Philox stream 3 inverse-CDF on the rollout's logits (vn_a2c.hip sample_kernel)
-    k = vdist.rank_seed(seed, 0)
-    lg = out[:, :A].numpy().astype(np.float32).reshape(T, E, A)
-    for t in range(T):
-        ctr = T * 1 + t  # updates so far x T + step
-        rr = philox.philox4x32_10(np.arange(E), ctr & 0xffffffff, ctr >> 32, philox.STREAM_POLICY,
-                                  k & 0xffffffff, k >> 32)[0]
-        u = (rr >> 8).astype(np.float32) * np.float32(1.0 / 16777216.0)
-        p = np.exp(lg[t] - lg[t].max(1, keepdims=True))
-        p = p / p.sum(1, keepdims=True)
-        cdf = np.cumsum(p, 1)
-        want = np.minimum((u[:, None] >= cdf[:, :A - 1]).sum(1), A - 1)
-        near = np.abs(u[:, None] - cdf[:, :A - 1]).min(1) < 1e-5
-        assert np.array_equal(want[~near], a2[t][~near]), t
-
-    sd = net.to_reference(p0)
-    ref = GoalNetOracle((174, 174)).load_reference(sd).double()
-    heads = AuxHeadsOracle().load_reference(sd).double()
-    lstm = torch.nn.LSTM(512 + A + 1, 512, batch_first=True).double()
-    for name in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
-        getattr(lstm, name).data.copy_(sd["rnn.inner." + name].double())
-    fl = lambda x: frames_to_float(torch.as_tensor(x)).double()  # noqa: E731
-    _, _, x4, pre = ref.forward_masked(fl(frames[rows_i]), fl(frames[rows_g]), masks)
-    _check_masks_are_signs(masks, pre)
-    x5 = (pre["z5"] * masks["m5"]).view(T, E, 512)
-    _, _, _, bpre = ref.forward_masked(fl(frames[brows[0]]), fl(frames[brows[1]]), bmasks)
-    xb = bpre["z5"] * bmasks["m5"]
-    h, c = h0[None], c0[None]
-    ys = []
-    for t in range(T):
-        m = lmask[t][None, :, None]
-        y, (h, c) = lstm(torch.cat((x5[t], lra[t]), 1)[:, None], (h * m, c * m))
-        ys.append(y[:, 0])
-    m = bmask[None, :, None]
-    yb, _ = lstm(torch.cat((xb, blra), 1)[:, None], (h * m, c * m))
-    y = torch.cat(ys)
-    logits, value = ref.policy_logits(y), ref.critic(y).view(-1)
-    vboot = ref.critic(yb[:, 0]).view(-1)
-    _check_outputs(out[:, :A].numpy(), out[:, A].numpy(), logits.detach().numpy(), value.detach().numpy())
-    assert _err(boot[:, A].numpy(), vboot.detach().numpy()) <= 1e-5
-    assert _elementwise(boot[:, A].numpy(), vboot.detach().numpy()) <= 1.0
-    vext = torch.cat([value.detach().view(T, E), vboot.detach().view(1, E)])
-    R = oa2c.returns(rewards.double(), dones, vext, 0.99)
-    loss, _ = oa2c.loss(logits, value, actions, R.view(-1))
-    preds, apre = heads.forward_masked(x4, amasks)
-    dd, ss = scene.depth, scene.segmentation
-    ph, pw = net.aux_layout["p_hw"]
-    tgt = [t_.double() for t_ in aux_targets(dd[rows_i], ss[rows_i], ss[rows_g], 4, (ph, pw))]
-    (loss + w * sum(torch.nn.functional.mse_loss(p, t_) for p, t_ in zip(preds, tgt))).backward()
-    mine = net.to_reference(grads)
-    errs = {}
-    for k_, attr in NAMES.items():
-        mod = getattr(ref, attr)
-        for kind in ("weight", "bias"):
-            errs[k_ + "." + kind] = _err(mine[k_ + "." + kind].numpy(), getattr(mod, kind).grad.numpy())
-    for name in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
-        errs[name] = _err(mine["rnn.inner." + name].numpy(), getattr(lstm, name).grad.numpy())
-    for hd, name in zip(heads.heads, AUX_NAMES):
-        for i, layer in ((1, hd[0]), (3, hd[2])):
-            for kind in ("weight", "bias"):
-                key = "%s.0.%d.%s" % (name, i, kind)
-                errs[key] = _err(mine[key].numpy(), getattr(layer, kind).grad.numpy())
+    from oracle.update_checks import maze_scene, second_update_vs_fp64
+    scene, graph, spd, frames = maze_scene((174, 174), aux=True)
+    res = second_update_vs_fp64(scene, graph, spd, frames, E=4, T=20, seed=3, env_seed=11, max_steps=25,
+                                aux_weight=0.1)
+    errs = res["errs"]
+    want = {k_ + "." + kind for k_ in NAMES for kind in ("weight", "bias")}
+    want |= {"rnn.inner." + name for name in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")}
+    want |= {"%s.0.%d.%s" % (name, i, kind) for name in AUX_NAMES for i in (1, 3) for kind in ("weight", "bias")}
+    assert set(errs) == want  # every tensor of the trunk, the heads, the LSTM and the aux heads
     bad = {k_: "%.3g" % e for k_, e in errs.items() if e > 1e-4}
     assert not bad, bad
     print("logged-run shape (174x174, LSTM + aux, 4 envs x 20): worst gradient error %.3g" % max(errs.values()))
