@@ -22,6 +22,9 @@
 // as the sequential rejection loop over the same counter stream.
 // The frames are streamed with 16-B lanes, 8 loads in flight per lane; with output reuse on
 // (vn_set_output_reuse) a frame whose output row already holds it is not copied.
+// vn_step_aux / vn_observe_aux (AuxiliaryGraph's five-tuple observation) are the same kernel
+// with a five-frame tail: depth, segmentation and goal segmentation rows leave the caller's
+// aux arenas in the same launch, under the same reuse rule, with records of their own (AuxRec).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -90,6 +93,21 @@ static_assert(sizeof(EnvRec) == 128, "one record per 128-B line");
 // on the device, so replayed graphs and interleaved vn_step / vn_step_f32 calls stay correct.
 constexpr uint64_t kOutF32 = 1ull << 63;
 
+// The output-reuse records of the three auxiliary frames (vn_step_aux / vn_observe_aux: depth,
+// segmentation, goal segmentation): EnvRec has 8 free words and these need 9, so they live in
+// an array of their own, allocated with vn_set_aux_arena and touched only by the five-frame
+// instantiations. Same meaning as RW_OUT_ROW / RW_OUT_ADDR, the rows being aux-arena rows.
+enum {
+  AW_ROW = 0,   // [3] aux-arena row last written to the depth / segmentation / goal segmentation row
+  AW_ADDR = 4,  // [3] x 64 bit: that output row's address | kOutF32 (0 matches nothing)
+  AW_USED = 10,
+  AW_WORDS = 16,
+};
+struct alignas(64) AuxRec {
+  int32_t w[AW_WORDS];
+};
+static_assert(sizeof(AuxRec) == 64, "one aux record per 64-B line");
+
 typedef int32_t i32x16 __attribute__((ext_vector_type(16), may_alias, aligned(64)));
 typedef int32_t i32x8 __attribute__((ext_vector_type(8), may_alias, aligned(32)));
 typedef int32_t i32x4 __attribute__((ext_vector_type(4), may_alias, aligned(16)));
@@ -150,6 +168,19 @@ struct EnvArgs {
   int px, ch;
 };
 
+// The five-frame instantiations' arguments (vn_step_aux / vn_observe_aux): EnvArgs, which
+// stays the kernel argument of every other instantiation, plus the aux arenas, the three
+// further outputs (any may be NULL: not written, record left alone) and their records.
+struct EnvAuxArgs : EnvArgs {
+  const uint8_t* depth_arena;  // [rows][px][dch]
+  const uint8_t* seg_arena;    // [rows][px][sch]
+  AuxRec* arecs;               // [n_envs]
+  uint8_t* out_depth;          // u8 [E][px][dch], or float [E][dch][px]
+  uint8_t* out_seg;
+  uint8_t* out_gseg;
+  int dch, sch;
+};
+
 // MODE_STEP_HEADS: a step of vn_step_a2c that also computes the policy heads (its own
 // instantiation, so the plain step keeps its register budget)
 enum { MODE_STEP = 0, MODE_RESET = 1, MODE_OBSERVE = 2, MODE_STEP_HEADS = 3 };
@@ -157,6 +188,17 @@ enum { MODE_STEP = 0, MODE_RESET = 1, MODE_OBSERVE = 2, MODE_STEP_HEADS = 3 };
 // rows (VEC = 16: the 4-pixel lanes of cvt_two_frames, VEC = 4: cvt_frames_scalar). Own
 // instantiations, so the u8 kernels are the code they were.
 enum { FMT_U8 = 0, FMT_F32 = 1 };
+// AUX = 1: the five-frame tail (image, goal, depth, segmentation, goal segmentation) of
+// vn_step_aux / vn_observe_aux, taking EnvAuxArgs. A template parameter of its own, so every
+// AUX = 0 instantiation keeps its code and its kernel argument.
+template <int AUX>
+struct env_args_of {
+  typedef EnvArgs type;
+};
+template <>
+struct env_args_of<1> {
+  typedef EnvAuxArgs type;
+};
 constexpr int kEnvsPerBlock = 4;
 constexpr int kStartRounds = 16;  // 1024 rejection attempts before flagging
 
@@ -497,6 +539,64 @@ __device__ __forceinline__ void cvt_one_frame(float* __restrict__ d, const uint8
   }
 }
 
+// A one-channel frame (the depth row of vn_step_aux): the row is its own plane. A lane owns the
+// same 4 consecutive pixels, group q: one 4-B load at byte 4 q (a wave instruction reads 256
+// contiguous bytes), 4 conversions, one 16-B nt store at float 4 q (1024 contiguous bytes).
+// Each group is converted and stored between scheduling barriers, as in cvt_store12, so a
+// trip's conversions are not all done before its first store.
+__device__ __forceinline__ uint32_t ld4(const uint8_t* __restrict__ s, int q) {
+  return *reinterpret_cast<const uint32_t*>(s + 4 * q);
+}
+__device__ __forceinline__ void cvt_store4(float* __restrict__ d, int q, const uint32_t w) {
+  __builtin_amdgcn_sched_barrier(0);
+  const f32x4 v = {unit_byte<0>(w), unit_byte<1>(w), unit_byte<2>(w), unit_byte<3>(w)};
+  __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(d + 4 * q));
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// cvt_one_frame's structure on one plane: 8 loads in flight per lane, a trip is 512 groups
+// (2048 pixels): 84 x 84 = 3 trips + 228, 64 x 64 = 2 trips exactly. A first trip with a fixed
+// load count around mid(), wave-uniform full trips, and a remainder whose predicated loads
+// are all issued before its stores.
+template <class Mid>
+__device__ __forceinline__ void cvt_one_plane(float* __restrict__ d, const uint8_t* __restrict__ s, int P, int lane,
+                                              Mid mid) {
+  constexpr int U = 8;
+  const int n = P >> 2;
+  int base = 0;
+  {  // first trip, mid() inside it: always U loads
+    const bool full = 64 * U <= n;  // wave-uniform
+    const int i0 = full ? lane : min(lane, n - 1), step = full ? 64 : 0;
+    uint32_t v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = ld4(s, i0 + step * u);
+    mid();
+    if (full) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) cvt_store4(d, lane + 64 * u, v[u]);
+      base = 64 * U;
+    }
+  }
+  for (; base + 64 * U <= n; base += 64 * U) {
+    const int i = base + lane;
+    uint32_t v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = ld4(s, i + 64 * u);
+#pragma unroll
+    for (int u = 0; u < U; ++u) cvt_store4(d, i + 64 * u, v[u]);
+  }
+  if (base < n) {
+    const int i = base + lane;
+    uint32_t v[U] = {};
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (i + 64 * u < n) v[u] = ld4(s, i + 64 * u);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (i + 64 * u < n) cvt_store4(d, i + 64 * u, v[u]);
+  }
+}
+
 // The fallback (P % 4 != 0, channels != 3 or planes that are only 4-B aligned): one element
 // per lane and trip, plane by plane. d2 / s2 may be NULL (one frame).
 __device__ __forceinline__ void cvt_frames_scalar(float* __restrict__ d1, const uint8_t* __restrict__ s1,
@@ -531,8 +631,50 @@ __device__ __forceinline__ void store_out_record(EnvRec* R, int32_t row1, int32_
       i32x4{(int32_t)(uint32_t)a1, (int32_t)(uint32_t)(a1 >> 32), (int32_t)(uint32_t)a2, (int32_t)(uint32_t)(a2 >> 32)};
 }
 
-template <int MODE, int VEC, int FMT = FMT_U8>
-__global__ __launch_bounds__(256) void env_kernel(EnvArgs a) {
+// One frame of the five-frame tail (vn_step_aux): its output row, its arena row, the row's
+// elements and channels. VEC / FMT pick the loop as in the two-frame tails; the float vector
+// form is launched only for 3-channel frames with a 1-channel depth, which takes cvt_one_plane.
+struct AuxFrame {
+  uint8_t* d;
+  const uint8_t* s;
+  int64_t n;
+  int ch;
+};
+// frame k of the five: image, goal, depth, segmentation, goal segmentation
+__device__ __forceinline__ AuxFrame aux_frame(const EnvAuxArgs& a, int k, int32_t img_row, int32_t goal_row, int64_t n0,
+                                              int64_t n2, int64_t n3, uint8_t* d0, uint8_t* d1, uint8_t* d2,
+                                              uint8_t* d3, uint8_t* d4) {
+  const int32_t row = (k == 1 || k == 4) ? goal_row : img_row;
+  const uint8_t* base = k < 2 ? a.arena : k == 2 ? a.depth_arena : a.seg_arena;
+  const int64_t n = k < 2 ? n0 : k == 2 ? n2 : n3;
+  return AuxFrame{k == 0 ? d0 : k == 1 ? d1 : k == 2 ? d2 : k == 3 ? d3 : d4, base + (int64_t)row * n, n,
+                  k < 2 ? a.ch : k == 2 ? a.dch : a.sch};
+}
+template <int VEC, int FMT, class Mid>
+__device__ __forceinline__ void write_one_frame(const AuxFrame f, int P, int lane, Mid mid) {
+  if constexpr (FMT == FMT_U8) {
+    copy_one_frame<VEC>(f.d, f.s, f.n, lane, mid);
+  } else if constexpr (VEC == 16) {
+    if (f.ch == 1)
+      cvt_one_plane(reinterpret_cast<float*>(f.d), f.s, P, lane, mid);
+    else
+      cvt_one_frame(reinterpret_cast<float*>(f.d), f.s, P, lane, mid);
+  } else {
+    mid();
+    cvt_frames_scalar(reinterpret_cast<float*>(f.d), f.s, nullptr, nullptr, P, f.ch, lane);
+  }
+}
+
+__device__ __forceinline__ void store_aux_record(AuxRec* A, int32_t r0, int32_t r1, int32_t r2, uint64_t a0,
+                                                 uint64_t a1, uint64_t a2) {
+  *reinterpret_cast<i32x4*>(A->w + AW_ROW) = i32x4{r0, r1, r2, 0};
+  *reinterpret_cast<i32x4*>(A->w + AW_ADDR) =
+      i32x4{(int32_t)(uint32_t)a0, (int32_t)(uint32_t)(a0 >> 32), (int32_t)(uint32_t)a1, (int32_t)(uint32_t)(a1 >> 32)};
+  *reinterpret_cast<i32x2*>(A->w + AW_ADDR + 4) = i32x2{(int32_t)(uint32_t)a2, (int32_t)(uint32_t)(a2 >> 32)};
+}
+
+template <int MODE, int VEC, int FMT = FMT_U8, int AUX = 0>
+__global__ __launch_bounds__(256) void env_kernel(typename env_args_of<AUX>::type a) {
   const int lane = threadIdx.x & 63;
   const int e = uni(blockIdx.x * kEnvsPerBlock + (threadIdx.x >> 6));
   if (e >= a.n_envs) return;
@@ -550,6 +692,9 @@ __global__ __launch_bounds__(256) void env_kernel(EnvArgs a) {
   const int32_t rec_r1 = hi[RW_OUT_ROW - 16], rec_r2 = hi[RW_OUT_ROW + 1 - 16];
   const uint64_t rec_a1 = (uint32_t)hi[RW_OUT_ADDR - 16] | ((uint64_t)(uint32_t)hi[RW_OUT_ADDR + 1 - 16] << 32);
   const uint64_t rec_a2 = (uint32_t)hi[RW_OUT_ADDR + 2 - 16] | ((uint64_t)(uint32_t)hi[RW_OUT_ADDR + 3 - 16] << 32);
+  // the aux frames' record, issued with the two loads above (five-frame instantiations only)
+  i32x16 ax = {};
+  if constexpr (AUX != 0) ax = *reinterpret_cast<const i32x16*>(a.arecs[e].w);
 
   // the caller's action, loaded together with the record (vn_step_a2c samples its own)
   int act_in = 0;
@@ -713,7 +858,56 @@ __global__ __launch_bounds__(256) void env_kernel(EnvArgs a) {
     emit(false, 0, 0, 0, 0);
     return;
   }
-  if constexpr (FMT == FMT_F32) {
+  if constexpr (AUX != 0) {
+    // The five-frame tail: frame k = image, goal, depth, segmentation, goal segmentation, the
+    // last three from the aux arenas at img_row / img_row / goal_row. One frame at a time
+    // through the one-frame loops, each frame kept or written by the rule of the two-frame
+    // tails (all decisions wave-uniform); lane 0's stores run inside the first trip of the
+    // first frame written, or alone when all five are kept. A NULL aux output is never
+    // written and keeps its record.
+    constexpr uint64_t fbit = FMT == FMT_F32 ? kOutF32 : 0;
+    constexpr int ES = FMT == FMT_F32 ? 4 : 1;  // bytes per output element
+    const int P = a.px;
+    const int64_t n0 = a.frame_bytes, n2 = (int64_t)P * a.dch, n3 = (int64_t)P * a.sch;  // elements per row
+    uint8_t* d0 = a.obs + (int64_t)e * n0 * ES;
+    uint8_t* d1 = a.goal_out + (int64_t)e * n0 * ES;
+    uint8_t* d2 = a.out_depth ? a.out_depth + (int64_t)e * n2 * ES : nullptr;
+    uint8_t* d3 = a.out_seg ? a.out_seg + (int64_t)e * n3 * ES : nullptr;
+    uint8_t* d4 = a.out_gseg ? a.out_gseg + (int64_t)e * n3 * ES : nullptr;
+    const uint64_t t0 = (uint64_t)d0 | fbit, t1 = (uint64_t)d1 | fbit, t2 = (uint64_t)d2 | fbit,
+                   t3 = (uint64_t)d3 | fbit, t4 = (uint64_t)d4 | fbit;
+    const int32_t xr2 = ax[AW_ROW], xr3 = ax[AW_ROW + 1], xr4 = ax[AW_ROW + 2];
+    const uint64_t xa2 = (uint32_t)ax[AW_ADDR] | ((uint64_t)(uint32_t)ax[AW_ADDR + 1] << 32);
+    const uint64_t xa3 = (uint32_t)ax[AW_ADDR + 2] | ((uint64_t)(uint32_t)ax[AW_ADDR + 3] << 32);
+    const uint64_t xa4 = (uint32_t)ax[AW_ADDR + 4] | ((uint64_t)(uint32_t)ax[AW_ADDR + 5] << 32);
+    int todo = 0;  // bit k: frame k is written by this launch
+    if (!(a.reuse && rec_a1 == t0 && rec_r1 == img_row)) todo |= 1;
+    if (!(a.reuse && rec_a2 == t1 && rec_r2 == goal_row)) todo |= 2;
+    if (d2 && !(a.reuse && xa2 == t2 && xr2 == img_row)) todo |= 4;
+    if (d3 && !(a.reuse && xa3 == t3 && xr3 == img_row)) todo |= 8;
+    if (d4 && !(a.reuse && xa4 == t4 && xr4 == goal_row)) todo |= 16;
+    auto mid = [&]() __attribute__((always_inline)) {
+      emit(true, img_row, goal_row, t0, t1);
+      if (lane == 0)
+        store_aux_record(a.arecs + e, d2 ? img_row : xr2, d3 ? img_row : xr3, d4 ? goal_row : xr4, d2 ? t2 : xa2,
+                         d3 ? t3 : xa3, d4 ? t4 : xa4);
+    };
+    if (todo == 0) {
+      mid();
+    } else {
+      // the first frame written carries lane 0's stores, so what they store is dead after its
+      // first trip; the others follow through the same loops with nothing in the middle
+      write_one_frame<VEC, FMT>(aux_frame(a, __builtin_ctz(todo), img_row, goal_row, n0, n2, n3, d0, d1, d2, d3, d4), P,
+                                lane, mid);
+      todo &= todo - 1;
+#pragma nounroll
+      while (todo != 0) {
+        write_one_frame<VEC, FMT>(aux_frame(a, __builtin_ctz(todo), img_row, goal_row, n0, n2, n3, d0, d1, d2, d3, d4),
+                                  P, lane, []() {});
+        todo &= todo - 1;
+      }
+    }
+  } else if constexpr (FMT == FMT_F32) {
     // the float tail: the rows of the u8 tail below, F floats each, addresses recorded with
     // kOutF32 (a u8 record never matches here, nor a float record there)
     const int64_t F = a.frame_bytes;
@@ -897,6 +1091,12 @@ struct vn_ctx {
   // output reuse: the host switch (what each env last wrote is in its record)
   int reuse = 0;       // vn_set_output_reuse
   int reuse_arm = 0;   // the next two-frame launch still writes every row
+  // vn_set_aux_arena: the caller's depth / segmentation arenas (borrowed) and the aux
+  // frames' output records (owned, allocated with the first arena)
+  const uint8_t* depth_arena = nullptr;
+  const uint8_t* seg_arena = nullptr;
+  int depth_ch = 0, seg_ch = 0;
+  AuxRec* arecs = nullptr;
 };
 
 namespace {
@@ -993,10 +1193,74 @@ int launch_env_f32(vn_ctx* c, const EnvArgs& a, hipStream_t stream) {
   return VN_OK;
 }
 
+// vn_step_aux / vn_observe_aux: `base` holds everything but the frames. Checks the output set,
+// then launches the five-frame instantiation whose lane width every written row allows: for
+// u8 the widest of 16 / 4 / 1 bytes that divides all three row sizes and both ends of every
+// row; for f32 the 4-pixel lanes when the frames are 3 + 3 + 1 channels of a multiple of 4
+// pixels with 16-B aligned planes, else the scalar form. Nothing is launched on an error.
+template <int MODE>
+int launch_env_aux(vn_ctx* c, const EnvArgs& base, const vn_obs_set* o, const char* who, hipStream_t stream) {
+  const std::string w(who);
+  if (!o) return fail(VN_EINVAL, w + ": obs is NULL");
+  if (!c->depth_arena || !c->seg_arena || !c->arecs) return fail(VN_EINVAL, w + ": no aux arena (vn_set_aux_arena)");
+  if (o->format != VN_OBS_U8_HWC && o->format != VN_OBS_F32_CHW) return fail(VN_EINVAL, w + ": unknown format");
+  if (!o->image || !o->goal) return fail(VN_EINVAL, w + ": image and goal must not be NULL");
+  const bool f32 = o->format == VN_OBS_F32_CHW;
+  const int64_t P = c->px, es = f32 ? 4 : 1;
+  const int64_t elems[5] = {c->frame_bytes, c->frame_bytes, P * c->depth_ch, P * c->seg_ch, P * c->seg_ch};
+  const uintptr_t outs[5] = {(uintptr_t)o->image, (uintptr_t)o->goal, (uintptr_t)o->depth, (uintptr_t)o->segmentation,
+                             (uintptr_t)o->goal_segmentation};
+  uintptr_t all = 0;
+  for (int k = 0; k < 5; ++k) all |= outs[k];
+  if (f32 && (all & 3)) return fail(VN_EINVAL, w + ": float outputs must be 4-byte aligned");
+  for (int i = 0; i < 5; ++i) {
+    for (int j = i + 1; j < 5; ++j) {
+      if (!outs[i] || !outs[j]) continue;
+      const uintptr_t ei = outs[i] + (uintptr_t)(c->n_envs * elems[i] * es);
+      const uintptr_t ej = outs[j] + (uintptr_t)(c->n_envs * elems[j] * es);
+      if (outs[i] < ej && outs[j] < ei) return fail(VN_EINVAL, w + ": two outputs overlap");
+    }
+  }
+  EnvAuxArgs a;
+  std::memset(&a, 0, sizeof(a));
+  static_cast<EnvArgs&>(a) = base;
+  a.obs = reinterpret_cast<uint8_t*>(o->image);
+  a.goal_out = reinterpret_cast<uint8_t*>(o->goal);
+  a.out_depth = reinterpret_cast<uint8_t*>(o->depth);
+  a.out_seg = reinterpret_cast<uint8_t*>(o->segmentation);
+  a.out_gseg = reinterpret_cast<uint8_t*>(o->goal_segmentation);
+  a.depth_arena = c->depth_arena;
+  a.seg_arena = c->seg_arena;
+  a.arecs = c->arecs;
+  a.dch = c->depth_ch;
+  a.sch = c->seg_ch;
+  a.reuse = take_reuse(c, o->image, o->goal, stream);
+  const dim3 grid((c->n_envs + kEnvsPerBlock - 1) / kEnvsPerBlock), block(64 * kEnvsPerBlock);
+  const uintptr_t ends = all | (uintptr_t)c->depth_arena | (uintptr_t)c->seg_arena;
+  if (f32) {
+    const bool vec = c->channels == 3 && c->seg_ch == 3 && c->depth_ch == 1 && P % 4 == 0 && all % 16 == 0 &&
+                     ((uintptr_t)c->depth_arena | (uintptr_t)c->seg_arena) % 4 == 0;
+    if (vec)
+      hipLaunchKernelGGL((env_kernel<MODE, 16, FMT_F32, 1>), grid, block, 0, stream, a);
+    else
+      hipLaunchKernelGGL((env_kernel<MODE, 4, FMT_F32, 1>), grid, block, 0, stream, a);
+  } else {
+    const int64_t sizes = elems[0] | elems[2] | elems[3];
+    if (sizes % 16 == 0 && ends % 16 == 0)
+      hipLaunchKernelGGL((env_kernel<MODE, 16, FMT_U8, 1>), grid, block, 0, stream, a);
+    else if (sizes % 4 == 0 && ends % 4 == 0)
+      hipLaunchKernelGGL((env_kernel<MODE, 4, FMT_U8, 1>), grid, block, 0, stream, a);
+    else
+      hipLaunchKernelGGL((env_kernel<MODE, 1, FMT_U8, 1>), grid, block, 0, stream, a);
+  }
+  VN_HIP(hipGetLastError());
+  return VN_OK;
+}
+
 void free_ctx(vn_ctx* c) {
   if (!c) return;
   void* ptrs[] = {c->arena, c->graph, c->spd, c->scenes, c->recs, c->env_scene,
-                  c->tasks, c->sched, c->flags, c->cur_order, c->cur_count};
+                  c->tasks, c->sched, c->flags, c->cur_order, c->cur_count, c->arecs};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete c;
@@ -1220,6 +1484,56 @@ int vn_step_f32(vn_ctx* c, const int32_t* actions_dev, float* obs_chw_dev, float
   a.state_out = state_dev;
   a.reuse = take_reuse(c, obs_chw_dev, goal_chw_dev, (hipStream_t)stream);
   return launch_env_f32<MODE_STEP>(c, a, (hipStream_t)stream);
+}
+
+int vn_set_aux_arena(vn_ctx* c, const uint8_t* depth_dev, int depth_channels, const uint8_t* seg_dev,
+                     int seg_channels) {
+  if (!c) return fail(VN_EINVAL, "vn_set_aux_arena: NULL ctx");
+  if (!depth_dev && !seg_dev) {  // clear: the records stay allocated, nothing reads them
+    c->depth_arena = c->seg_arena = nullptr;
+    c->depth_ch = c->seg_ch = 0;
+    return VN_OK;
+  }
+  if (!depth_dev || !seg_dev) return fail(VN_EINVAL, "vn_set_aux_arena: need both arenas (or both NULL)");
+  if (depth_channels <= 0 || seg_channels <= 0) return fail(VN_EINVAL, "vn_set_aux_arena: bad channel count");
+  if ((int64_t)c->px * std::max(depth_channels, seg_channels) >= (1ll << 31))
+    return fail(VN_EINVAL, "vn_set_aux_arena: rows of 2^31 bytes or more");
+  DeviceGuard guard(c->device);
+  const size_t bytes = (size_t)c->n_envs * sizeof(AuxRec);
+  if (!c->arecs && hipMalloc((void**)&c->arecs, bytes) != hipSuccess) {
+    c->arecs = nullptr;
+    return fail(VN_ENOMEM, "vn_set_aux_arena: device allocation failed");
+  }
+  // null addresses match no destination: new arenas are other bytes, so every aux row is
+  // written once more (after any launch still using the old records)
+  VN_HIP(hipDeviceSynchronize());
+  VN_HIP(hipMemset(c->arecs, 0, bytes));
+  c->depth_arena = depth_dev;
+  c->seg_arena = seg_dev;
+  c->depth_ch = depth_channels;
+  c->seg_ch = seg_channels;
+  return VN_OK;
+}
+
+int vn_observe_aux(vn_ctx* c, const vn_obs_set* obs, int32_t* state_dev, vn_stream_t stream) {
+  if (!c) return fail(VN_EINVAL, "vn_observe_aux: NULL ctx");
+  DeviceGuard guard(c->device);
+  EnvArgs a = make_args(c);
+  a.state_out = state_dev;
+  return launch_env_aux<MODE_OBSERVE>(c, a, obs, "vn_observe_aux", (hipStream_t)stream);
+}
+
+int vn_step_aux(vn_ctx* c, const int32_t* actions_dev, const vn_obs_set* obs, float* reward_dev, uint8_t* done_dev,
+                int32_t* state_dev, vn_stream_t stream) {
+  if (!c) return fail(VN_EINVAL, "vn_step_aux: NULL ctx");
+  if (!actions_dev) return fail(VN_EINVAL, "vn_step_aux: actions is NULL");
+  DeviceGuard guard(c->device);
+  EnvArgs a = make_args(c);
+  a.actions = actions_dev;
+  a.reward = reward_dev;
+  a.done = done_dev;
+  a.state_out = state_dev;
+  return launch_env_aux<MODE_STEP>(c, a, obs, "vn_step_aux", (hipStream_t)stream);
 }
 
 int vn_step_a2c(vn_ctx* c, const vn_a2c_step* p, float* reward_dev, uint8_t* done_dev, int32_t* state_dev,

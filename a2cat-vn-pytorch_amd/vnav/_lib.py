@@ -65,6 +65,21 @@ class A2CStep(ctypes.Structure):
     ]
 
 
+class ObsSet(ctypes.Structure):
+    """vn_obs_set (include/vnav.h): the five outputs of vn_step_aux / vn_observe_aux."""
+    _fields_ = [
+        ("image", c_void_p),
+        ("goal", c_void_p),
+        ("depth", c_void_p),
+        ("segmentation", c_void_p),
+        ("goal_segmentation", c_void_p),
+        ("format", c_int32),
+    ]
+
+
+OBS_U8_HWC, OBS_F32_CHW = 0, 1  # vn_obs_set.format
+
+
 class GoalRuns(ctypes.Structure):
     """vn_goal_runs (include/vnav.h)."""
     _fields_ = [
@@ -122,6 +137,9 @@ SIGNATURES = {
     "vn_num_envs": (c_int, [c_void_p]),
     "vn_gather_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "vn_step_a2c": (c_int, [c_void_p, P(A2CStep), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vn_set_aux_arena": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int]),
+    "vn_observe_aux": (c_int, [c_void_p, P(ObsSet), c_void_p, c_void_p]),
+    "vn_step_aux": (c_int, [c_void_p, c_void_p, P(ObsSet), c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 SIGNATURES.update({

@@ -13,8 +13,13 @@ itself then emits float32 ``[E,C,H,W]`` in [0, 1] (``vn_step_f32``), with the wr
 arithmetic bit for bit. ``to_float_chw`` below is the same chain in torch, for frames that
 are already out of the env; the policy kernels consume the uint8 frames directly and fuse
 that conversion.
+
+``aux_observations=True`` (AuxiliaryGraph-v0) makes the observation the reference's five-tuple
+``(image, goal, depth, segmentation, goal segmentation)``; with the aux frames in the format of
+the image frames all five leave the scene cache in the step's own launch (``vn_step_aux``).
 """
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -23,6 +28,7 @@ from . import _lib
 from .scenes import Scene
 
 OBS_FORMATS = ("u8_hwc", "f32_chw")
+AUX_KEYS = ("depth", "segmentation", "goal_segmentation")
 ST_FIELDS = ("scene", "state", "goal", "obs_state", "elapsed", "episode", "sched_pos")
 
 
@@ -36,15 +42,22 @@ class VectorEnv:
 
     def __init__(self, scenes, num_envs, seed=0, device=None, max_episode_steps=900, tasks=None,
                  env_scenes=None, autoreset=True, aux_observations=False, reuse_outputs=True,
-                 obs_format="u8_hwc"):
+                 obs_format="u8_hwc", aux_format=None):
         """obs_format: "u8_hwc" (default) returns and takes uint8 [E,H,W,C] frames; "f32_chw"
         returns and takes float32 [E,C,H,W] frames in [0, 1], every value float(u8) / 255 as
         fp32 division (ScaledFloatFrame's), converted in the step's own launch with the same
-        ``out=`` fast path and reuse contract. The extra depth / segmentation frames of
-        ``aux_observations=True`` stay uint8 [E,H,W,C] in either format. ``obs_shape`` is the
-        shape of one returned frame."""
+        ``out=`` fast path and reuse contract. ``obs_shape`` is the shape of one returned frame.
+        aux_format: the format of the extra depth / segmentation frames of
+        ``aux_observations=True``. None or "u8_hwc" (default): uint8 [E,H,W,1] / [E,H,W,3] in
+        either obs_format; "f32_chw": float32 [E,1,H,W] / [E,3,H,W], only together with
+        ``obs_format="f32_chw"``. When both formats are equal the five frames are written by one
+        launch (vn_step_aux) and ``out=`` may carry the three aux buffers (``step``)."""
         if obs_format not in OBS_FORMATS:
             raise ValueError("obs_format must be one of %s, got %r" % (OBS_FORMATS, obs_format))
+        if aux_format is not None and aux_format not in OBS_FORMATS:
+            raise ValueError("aux_format must be None or one of %s, got %r" % (OBS_FORMATS, aux_format))
+        if aux_format == "f32_chw" and obs_format != "f32_chw":
+            raise ValueError('aux_format="f32_chw" needs obs_format="f32_chw" (got %r)' % (obs_format,))
         if isinstance(scenes, Scene):
             scenes = [scenes]
         if not scenes:
@@ -94,6 +107,7 @@ class VectorEnv:
         # recaptured (A2CTrainer checks it before each replay)
         self.config_generation = 0
         self._out_cache = None
+        self._aux_cache = None
         # output reuse (vn_set_output_reuse): armed only while the caller
         # steps into its own buffers; _reuse_on mirrors the native switch
         self.reuse_outputs = bool(reuse_outputs)
@@ -127,6 +141,16 @@ class VectorEnv:
         self.aux_observations = bool(aux_observations)
         if self.aux_observations and self.aux_arena is None:
             raise ValueError("aux_observations needs depth + segmentation on every scene")
+        self.aux_format = aux_format or "u8_hwc"
+        self._aux_dtype = torch.float32 if self.aux_format == "f32_chw" else torch.uint8
+        # all five frames in one format: the five-frame entry points (vn_step_aux). The mixed
+        # pair (float image / goal, uint8 aux frames) stays vn_step_f32 + three row gathers
+        self._aux_fused = self.aux_observations and self.aux_format == self.obs_format
+        H, W = self.frame_shape[:2]
+        if self.aux_arena is not None:
+            dc, sc = int(self.aux_arena[0].shape[3]), int(self.aux_arena[1].shape[3])
+            chw = self.aux_format == "f32_chw"
+            self.aux_shapes = tuple((c, H, W) if chw else (H, W, c) for c in (dc, sc, sc))
 
     def _build_aux_arena(self):
         """Depth [rows,H,W,1] and segmentation [rows,H,W,3] uint8 on the device, indexed by
@@ -138,6 +162,11 @@ class VectorEnv:
         for s, b in zip(self.scenes, bases):
             depth[b:b + s.n_states].copy_(torch.from_numpy(s.depth))
             seg[b:b + s.n_states].copy_(torch.from_numpy(s.segmentation))
+        # the context borrows both tensors (kept alive as self.aux_arena) for vn_step_aux
+        torch.cuda.synchronize(self.device)
+        self.config_generation += 1
+        _lib.check(self.lib.vn_set_aux_arena(self._ctx, _lib.ptr(depth), int(depth.shape[3]), _lib.ptr(seg),
+                                             int(seg.shape[3])), "vn_set_aux_arena")
         return depth, seg
 
     def _gather_aux(self):
@@ -260,6 +289,7 @@ class VectorEnv:
             _lib.check(self.lib.vn_set_output_reuse(self._ctx, 0), "vn_set_output_reuse")
             self._reuse_on = False
             self._out_cache = None
+            self._aux_cache = None
 
     def reset(self, mask=None):
         m = None
@@ -272,10 +302,13 @@ class VectorEnv:
 
     def observe(self, out=None, gather=True):
         """Current (image, goal) frames in the env's obs_format; gather=False only refreshes
-        info img_row/goal_row."""
+        info img_row/goal_row. With ``aux_observations=True`` the five-tuple, and ``out`` may be
+        the five buffers (image, goal, depth, segmentation, goal segmentation)."""
         if not gather:
             _lib.check(self._vn_observe(self._ctx, None, None, None, self._stream()), "vn_observe")
             return None, None
+        if self._aux_fused and self._fused(out is not None, out is not None and len(out) > 2):
+            return self._observe_aux(out)
         img, goal = out if out is not None else self._frames()
         self._check_frames_out(img, goal)
         if out is None:
@@ -304,7 +337,12 @@ class VectorEnv:
         previous step (the goal between resets, the image on a blocked move), so the image and
         goal rows must be left as the env wrote them until the next step. Rows that are edited
         in place, shared between two envs or written by anything else need
-        ``VectorEnv(..., reuse_outputs=False)``, which writes every row on every step."""
+        ``VectorEnv(..., reuse_outputs=False)``, which writes every row on every step.
+        With ``aux_observations=True`` and the aux frames in the image frames' format, ``out``
+        may also carry ``depth``, ``segmentation`` and ``goal_segmentation`` (all three or none):
+        the five frames returned are then the caller's own tensors, under the same contract
+        (depth and segmentation are skipped with the image, goal segmentation with the goal),
+        and no two of the five may overlap."""
         if type(actions) is torch.Tensor and actions.dtype == torch.int32 and actions.device == self.device \
                 and actions.shape == (self.num_envs,) and actions.is_contiguous():
             a = actions
@@ -315,6 +353,9 @@ class VectorEnv:
             a = a.contiguous()
             if a.shape != (self.num_envs,):
                 raise ValueError("actions must have shape [num_envs]")
+        if self._aux_fused and gather and \
+                self._fused(out is not None, out is not None and any(out.get(k) is not None for k in AUX_KEYS)):
+            return self._step_aux(a, out)
         if out is not None and gather:
             # the same caller-owned buffers as the previous call: validated then, pointers cached.
             # The key also holds each buffer's current data_ptr and size, so a tensor that was
@@ -349,6 +390,7 @@ class VectorEnv:
                 bufs = (img, goal, reward, done, state)
                 self._out_cache = (bufs, tuple(_lib.ptr(t) for t in bufs),
                                    tuple((t.data_ptr(), t.numel()) if t is not None else None for t in bufs))
+                self._aux_cache = None
                 self._arm_reuse()
         _lib.check(self._vn_step(self._ctx, _lib.ptr(a), _lib.ptr(img), _lib.ptr(goal), _lib.ptr(reward),
                                  _lib.ptr(done), _lib.ptr(state), self._stream()), "vn_step")
@@ -358,6 +400,107 @@ class VectorEnv:
         if self.aux_observations and gather:
             return (img, goal) + self._gather_aux(), reward, done, info
         return (img, goal), reward, done, info
+
+    # -- the five-frame observation in one launch (vn_step_aux / vn_observe_aux) ------------
+    def _fused(self, has_out, has_aux_bufs):
+        """Whether this call takes the five-frame entry points. Not with VN_AUX_OBS_GATHER=1
+        (read per call: the former step + three vn_gather_rows, for the A/B test and the
+        measurement; uint8 aux frames only, float ones have no former form), and not when the
+        caller gives image / goal buffers but no uint8 aux buffers: then the aux frames are
+        fresh tensors gathered after the two-frame step, which keeps its output reuse."""
+        if not self._aux_fused:
+            return False
+        if self.aux_format == "u8_hwc":
+            if os.environ.get("VN_AUX_OBS_GATHER", "0") not in ("", "0"):
+                return False
+            if has_out and not has_aux_bufs:
+                return False
+        return True
+
+    def _aux_frames(self):
+        return tuple(torch.empty((self.num_envs,) + s, dtype=self._aux_dtype, device=self.device)
+                     for s in self.aux_shapes)
+
+    def _check_five(self, frames):
+        """The caller's five frame buffers: each as _check_out wants it, no two overlapping."""
+        self._check_frames_out(frames[0], frames[1])
+        if any(t is None for t in frames[2:]):
+            raise ValueError("out needs all of %s or none of them" % (AUX_KEYS,))
+        for name, t, shape in zip(AUX_KEYS, frames[2:], self.aux_shapes):
+            self._check_out(name, t, self._aux_dtype, self.num_envs * int(np.prod(shape)))
+        spans = sorted((t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in frames)
+        for (_, end), (start, _) in zip(spans, spans[1:]):
+            if start < end:
+                raise ValueError("the five frame buffers must not overlap")
+
+    def _obs_set(self, frames):
+        return _lib.ObsSet(*[t.data_ptr() for t in frames],
+                           _lib.OBS_F32_CHW if self.aux_format == "f32_chw" else _lib.OBS_U8_HWC)
+
+    def _aux_out_frames(self, given):
+        """The five frames of a call with caller-owned buffers: `given` holds image, goal and
+        either the three aux buffers or None x 3 (fresh aux tensors: the float form only, and
+        every such call writes all five, since a fresh tensor may lie at a recorded address)."""
+        if all(t is None for t in given[2:]):
+            self._check_frames_out(given[0], given[1])
+            self._aux_cache = None
+            return tuple(given[:2]) + self._aux_frames()
+        self._check_five(given)
+        return tuple(given)
+
+    def _observe_aux(self, out):
+        if out is None:
+            self._disarm_reuse()
+            frames = self._frames() + self._aux_frames()
+        else:
+            out = tuple(out)
+            if len(out) not in (2, 5):
+                raise ValueError("observe(out=...) takes (image, goal) or the five frame buffers")
+            frames = self._aux_out_frames(out + (None,) * (5 - len(out)))
+            self._arm_reuse()
+        o = self._obs_set(frames)
+        _lib.check(self.lib.vn_observe_aux(self._ctx, ctypes.byref(o), None, self._stream()), "vn_observe_aux")
+        return frames
+
+    def _step_aux(self, a, out):
+        E = self.num_envs
+        if out is not None:
+            bufs = (out["image"], out["goal"], out.get("reward"), out.get("done"), out.get("state")) + \
+                tuple(out.get(k) for k in AUX_KEYS)
+            c = self._aux_cache
+            if c is not None and all(x is y for x, y in zip(bufs, c[0])) and \
+                    c[2] == tuple((t.data_ptr(), t.numel()) if t is not None else None for t in bufs):
+                P = c[1]
+                _lib.check(self.lib.vn_step_aux(self._ctx, _lib.ptr(a), c[3], P[2], P[3], P[4], self._stream()),
+                           "vn_step_aux")
+                info = dict(self._info)
+                info["state"] = bufs[4]
+                return (bufs[0], bufs[1]) + bufs[5:], bufs[2], bufs[3], info
+        if out is None:
+            self._disarm_reuse()
+            frames = self._frames() + self._aux_frames()
+            reward = torch.empty(E, dtype=torch.float32, device=self.device)
+            done = torch.empty(E, dtype=torch.bool, device=self.device)
+            state = torch.empty(E, dtype=torch.int32, device=self.device)
+            o = self._obs_set(frames)
+        else:
+            reward, done, state = bufs[2:5]
+            frames = self._aux_out_frames(bufs[:2] + bufs[5:])
+            self._check_out("reward", reward, torch.float32, E)
+            self._check_out("done", done, torch.bool, E)
+            self._check_out("state", state, torch.int32, E)
+            o = self._obs_set(frames)
+            if bufs[5] is not None:
+                self._aux_cache = (bufs, tuple(_lib.ptr(t) for t in bufs),
+                                   tuple((t.data_ptr(), t.numel()) if t is not None else None for t in bufs),
+                                   ctypes.byref(o), o)
+                self._out_cache = None
+            self._arm_reuse()
+        _lib.check(self.lib.vn_step_aux(self._ctx, _lib.ptr(a), ctypes.byref(o), _lib.ptr(reward), _lib.ptr(done),
+                                        _lib.ptr(state), self._stream()), "vn_step_aux")
+        info = {k: v.clone() for k, v in self._info.items()} if out is None else dict(self._info)
+        info["state"] = state
+        return frames, reward, done, info
 
     def step_a2c(self, a2c, reward, done, state):
         """The trainer's rollout step (vn_step_a2c): the actions are sampled in the step from
@@ -446,7 +589,7 @@ def make(id, scenes, num_envs, **kwargs):
     if id not in REGISTRY:
         raise KeyError("unknown env id %r (known: %s)" % (id, sorted(REGISTRY)))
     opts = dict(REGISTRY[id])
-    opts.update(kwargs)
+    opts.update(kwargs)  # obs_format, aux_format, ... pass through
     return VectorEnv(scenes, num_envs, **opts)
 
 

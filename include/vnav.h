@@ -126,6 +126,62 @@ int vn_observe_f32(vn_ctx* ctx, float* obs_chw_dev, float* goal_chw_dev, int32_t
 int vn_step_f32(vn_ctx* ctx, const int32_t* actions_dev, float* obs_chw_dev, float* goal_chw_dev,
                 float* reward_dev, uint8_t* done_dev, int32_t* state_dev, vn_stream_t stream);
 
+/* ---- the five-frame observation of AuxiliaryGraph-v0 in the step's own launch ----
+ * GoalGymGraphAuxiliaryEnv.observe (environments/gym_graph/graph.py:96-120) returns (rgb, goal
+ * rgb, depth, segmentation, goal segmentation); experiments/thor_cached_auxiliary.py:76 makes
+ * that env.
+ *
+ * vn_set_aux_arena registers the depth [rows][H][W][depth_channels] and segmentation
+ * [rows][H][W][seg_channels] uint8 arenas (device memory, row-indexed like the frame arena:
+ * vn_frame_arena, vn_scene_row_base). The caller owns the memory and keeps it alive and
+ * unchanged while it is registered; the context only borrows it. Both pointers NULL clear the
+ * setting. Like the other vn_set_* calls it replaces launch arguments: a captured graph holds
+ * the old ones and must be recaptured. Setting arenas forgets what the aux outputs hold (their
+ * next write is a full one) and synchronises the device. */
+int vn_set_aux_arena(vn_ctx* ctx, const uint8_t* depth_dev, int depth_channels, const uint8_t* seg_dev,
+                     int seg_channels);
+
+enum {
+  VN_OBS_U8_HWC = 0,  /* uint8 [n_envs][H][W][C], the arenas' own layout */
+  VN_OBS_F32_CHW = 1, /* float [n_envs][C][H][W], float(u8) / 255 (vn_step_f32's arithmetic) */
+};
+/* The five outputs of one call, all in `format`. depth and segmentation are the aux-arena rows
+ * at the info img_row, goal_segmentation the segmentation row at the info goal_row (whatever the
+ * scene type: with companion frames goal_row is the companion row). In VN_OBS_U8_HWC the
+ * pointers are uint8_t*: image / goal [n_envs][H][W][C], depth [n_envs][H][W][depth_channels],
+ * the two segmentations [n_envs][H][W][seg_channels]. In VN_OBS_F32_CHW they are float*,
+ * 4-byte aligned: [n_envs][channels][H][W] each. */
+typedef struct vn_obs_set {
+  void* image;
+  void* goal;
+  void* depth;
+  void* segmentation;
+  void* goal_segmentation;
+  int32_t format;
+} vn_obs_set;
+/* vn_step / vn_observe (vn_step_f32 / vn_observe_f32 in VN_OBS_F32_CHW) with all five frames
+ * written by the one launch. Scalars, info buffers, flags, auto-reset and companion frames are
+ * theirs. image and goal must both be non-NULL; each of depth, segmentation, goal_segmentation
+ * may be NULL: that frame is not written and what the context recorded about it stays.
+ * Without an aux arena, or with two outputs that overlap, the call returns VN_EINVAL and
+ * launches nothing.
+ * Output reuse (vn_set_output_reuse) covers all five: per env and per output the context records
+ * the destination row's address (with its format) and the arena row last written there, and with
+ * reuse on a frame is skipped only when the recorded address is this launch's destination and the
+ * recorded row is the row to emit (depth and segmentation change with the image row, goal
+ * segmentation with the goal row). image and goal share their records with vn_step / vn_step_f32,
+ * so two-frame and five-frame calls may be mixed into the same buffers. The armed full write of
+ * vn_set_output_reuse(ctx, 1) writes all five, and a launch captured while armed is recorded as
+ * a full write of all five and leaves the arm alone. Added to that contract: within one call
+ * the five destinations do not overlap, and a caller who passes a buffer in another role than
+ * before (say the segmentation buffer as goal_segmentation) calls vn_set_output_reuse(ctx, 1)
+ * first. u8 rows take 16-byte lanes when H W is a multiple of 16 and every pointer is 16-byte
+ * aligned (4-byte lanes for multiples of 4, bytes otherwise); float rows take the vector path
+ * for 3 + 3 + 1 channels, H W a multiple of 4 and 16-byte aligned outputs. */
+int vn_observe_aux(vn_ctx* ctx, const vn_obs_set* obs, int32_t* state_dev, vn_stream_t stream);
+int vn_step_aux(vn_ctx* ctx, const int32_t* actions_dev, const vn_obs_set* obs, float* reward_dev,
+                uint8_t* done_dev, int32_t* state_dev, vn_stream_t stream);
+
 /* The A2C rollout's env step (the trainer's fast path; vn_step stays the gym/VecEnv
  * boundary): the action of env e is sampled in the step from the policy's output row e
  * (categorical over logits 0..A-1 of policy_out [E][8], Philox stream 3 with counter
