@@ -6,7 +6,9 @@ envs, float frames, other action counts) hold the kernels to the same bars with 
 code: the error measures, the reading of the activation store the forward wrote, the ReLU
 masks of the GPU forward (the oracle is run with them, see GoalNetOracle.forward_masked, and
 every disagreeing bit is asserted to be a tie), the comparison of the 14 (+ aux) parameter
-gradients, and the recurrent core against torch's float64 nn.LSTM (lstm_core_check).
+gradients, and the recurrent core against torch's float64 nn.LSTM (lstm_core_check). The
+BigHouse trunk's twins (_bighouse_masks, _bighouse_forward_masked, _ties_only,
+_bighouse_grads_vs_oracle) serve tests/test_bighouse_regimes_gpu.py and oracle/update_checks.py.
 
 Tolerances (north star): outputs and activations 1e-5, parameter gradients 1e-4 of each
 tensor's scale. Logits and values are also checked element by element: |gpu - fp64| <= 1e-5
@@ -24,6 +26,8 @@ from oracle.policy import trunk_sizes
 NAMES = {"shared_base.0.0": "conv1", "shared_base.0.2": "conv2", "conv_base.0.0": "conv3",
          "conv_base.0.2": "conv4", "conv_merge.0.1": "fc", "policy_logits.0": "policy_logits",
          "critic.0": "critic"}
+BIGHOUSE_NAMES = {"conv_base.0.0": "conv1", "conv_base.0.2": "conv2", "conv_base.0.4": "conv3",
+                  "conv_merge.0.1": "fc", "policy_logits.0": "policy_logits", "critic.0": "critic"}
 AUX_NAMES = ("deconv_depth", "deconv_mask", "deconv_mask_goal")
 LSTM_NAMES = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
 
@@ -102,6 +106,69 @@ def _check_masks_are_signs(masks, pre):
             assert worst <= 1e-5, "%s: mask disagrees with the oracle's sign at |z| = %.3g of scale" % (m, worst)
         flips[m] = int(bad.sum())
     return flips
+
+
+BIGHOUSE_PAIRS = {"m1": "z1", "m2": "z2", "m3": "z3", "m5": "z5"}
+
+
+def _bighouse_acts_views(net, acts, n):
+    """BigHouseModel's activation store [X1 | X2 | X3 | X5] (no conv4, no conv1 bitmask), each
+    sample-contiguous NHWC, of a store of capacity n."""
+    sz = [20 * 20 * 32, 9 * 9 * 64, 7 * 7 * 32, 512]
+    assert net.act_floats == sum(sz)
+    shapes = [(n, 20, 20, 32), (n, 9, 9, 64), (n, 7, 7, 32), (n, 512)]
+    out, p = {}, 0
+    for key, s, sh in zip(("X1", "X2", "X3", "X5"), sz, shapes):
+        out[key] = acts[p:p + n * s].view(sh)
+        p += n * s
+    return out
+
+
+def _bighouse_masks(net, acts, n):
+    """ReLU masks of BigHouseModel's trunk from its activation store [X1 | X2 | X3 | X5]. Read
+    them before the backward runs: it overwrites X1."""
+    out = {}
+    for key, x in zip(("m1", "m2", "m3", "m5"), _bighouse_acts_views(net, acts, n).values()):
+        x = x > 0
+        out[key] = (x.permute(0, 3, 1, 2) if x.dim() == 4 else x).double().cpu()
+    return out
+
+
+def _bighouse_forward_masked(ref, image, masks):
+    """BigHouseOracle.features with every ReLU replaced by its given mask -> (x3, f, pre)."""
+    pre = {}
+    pre["z1"] = z1 = ref.conv1(image)
+    pre["z2"] = z2 = ref.conv2(z1 * masks["m1"])
+    pre["z3"] = z3 = ref.conv3(z2 * masks["m2"])
+    x3 = z3 * masks["m3"]
+    pre["z5"] = z5 = ref.fc(x3.flatten(1))
+    return x3, z5 * masks["m5"], pre
+
+
+def _ties_only(masks, pre, pairs):
+    """_check_masks_are_signs over the given {mask: pre-activation} pairs -> flips per mask."""
+    flips = {}
+    for m, z in pairs.items():
+        zz = pre[z].detach()
+        bad = (masks[m] > 0) != (zz > 0)
+        if bad.any():
+            worst = float(zz[bad].abs().max() / zz.abs().max())
+            assert worst <= 1e-5, "%s: mask disagrees with the oracle's sign at |z| = %.3g of scale" % (m, worst)
+        flips[m] = int(bad.sum())
+    return flips
+
+
+def _bighouse_grads_vs_oracle(net, grads, ref, tol=1e-4):
+    """The 12 trunk + head gradient tensors by reference name -> {name: error of its scale}."""
+    mine = net.to_reference(grads)
+    errs = {}
+    for k, attr in BIGHOUSE_NAMES.items():
+        mod = getattr(ref, attr)
+        for kind in ("weight", "bias"):
+            errs[k + "." + kind] = _err(mine[k + "." + kind].numpy(), getattr(mod, kind).grad.numpy())
+    bad = {k: "%.3g" % e for k, e in errs.items() if not e <= tol}
+    assert not bad, bad
+    return errs
 
 
 def _grads_vs_oracle(net, grads, ref, heads=None, tol=1e-4):

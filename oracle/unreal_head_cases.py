@@ -34,32 +34,42 @@ def _cdiv(a, b):
     return (a + b - 1) // b
 
 
-def splitk(M, N, K, BM, BN):
-    """Slabs of a launch_gemm_x6_sk / launch_gemm_sk product (1 = the unsplit kernel with its own
-    epilogue): splitk_count, then kchunk and the recomputed count."""
+def splitk_chunk(M, N, K, BM, BN):
+    """(slabs, kchunk) of a launch_gemm_x6_sk / launch_gemm_sk product (1 slab = the unsplit kernel
+    with its own epilogue, kchunk = K): splitk_count, then kchunk and the recomputed count."""
     tiles = _cdiv(M, BM) * _cdiv(N, BN)
     if tiles >= SK_TILES or K < 4 * BK:
-        return 1
+        return 1, K
     splits = min(_cdiv(SK_WORKGROUPS, tiles), K // (2 * BK))
     while splits > 1 and splits * M * N > SK_CAP:
         splits -= 1
     splits = max(splits, 1)
     if splits <= 1:
-        return 1
+        return 1, K
     kchunk = _cdiv(_cdiv(K, splits), BK) * BK
-    return _cdiv(K, kchunk)
+    return _cdiv(K, kchunk), kchunk
 
 
-def wgrad_slabs(M, KP, P, BM, BN, bias):
-    """Slabs of launch_wgrad / launch_wgrad6 over P reduction rows (1 = the direct EpiWgrad
-    epilogue, else EpiSlab + launch_wgrad_reduce)."""
+def splitk(M, N, K, BM, BN):
+    """Slabs of a launch_gemm_x6_sk / launch_gemm_sk product (see splitk_chunk)."""
+    return splitk_chunk(M, N, K, BM, BN)[0]
+
+
+def wgrad_chunk(M, KP, P, BM, BN, bias):
+    """(slabs, kchunk) of launch_wgrad / launch_wgrad6 over P reduction rows (1 slab = the direct
+    EpiWgrad epilogue, else EpiSlab + launch_wgrad_reduce)."""
     N = KP + (1 if bias else 0)
     tiles = _cdiv(M, BM) * _cdiv(N, BN)
     splits = max(1, min(_cdiv(WGRAD_WORKGROUPS, tiles), _cdiv(P, WGRAD_ROWS)))
     while splits * M * N > SLAB and splits > 1:
         splits //= 2
     kchunk = _cdiv(_cdiv(P, splits), BK) * BK
-    return _cdiv(P, kchunk)
+    return _cdiv(P, kchunk), kchunk
+
+
+def wgrad_slabs(M, KP, P, BM, BN, bias):
+    """Slabs of launch_wgrad / launch_wgrad6 over P reduction rows (see wgrad_chunk)."""
+    return wgrad_chunk(M, KP, P, BM, BN, bias)[0]
 
 
 def reduce_lanes(M, N, splits):

@@ -35,11 +35,10 @@ from oracle import unreal as ou
 from oracle.policy import (BIGHOUSE_UNREAL_PARAM_ORDER, UNREAL_PARAM_ORDER, AuxHeadsOracle, BigHouseOracle,
                            GoalNetOracle, aux_targets, bighouse_pixel_control, bighouse_reward_prediction,
                            frames_to_float, pixel_control, reward_prediction)
-from oracle.trunk_checks import (AUX_NAMES, LSTM_NAMES, NAMES, _check_masks_are_signs, _check_outputs, _elementwise,
-                                 _err, _gpu_masks)
+from oracle.trunk_checks import (AUX_NAMES, BIGHOUSE_NAMES, LSTM_NAMES, NAMES, _bighouse_forward_masked,
+                                 _bighouse_masks, _check_masks_are_signs, _check_outputs, _elementwise, _err,
+                                 _gpu_masks, _ties_only)
 
-BIGHOUSE_NAMES = {"conv_base.0.0": "conv1", "conv_base.0.2": "conv2", "conv_base.0.4": "conv3",
-                  "conv_merge.0.1": "fc", "policy_logits.0": "policy_logits", "critic.0": "critic"}
 UNREAL_REWARDS = (1.0, 0.0, -0.1)  # goal, step, collision: the three reward-prediction classes
 
 # The composed-update cases of tests/test_unreal_update_gpu.py. E, S, T of the small ones are the
@@ -74,39 +73,6 @@ def maze_scene(hw, aux, rewards=None):
         scene = dataclasses.replace(scene, depth=rng.randint(0, 256, size=(ns, h, w, 1)).astype(np.uint8),
                                     segmentation=rng.randint(0, 256, size=(ns, h, w, 3)).astype(np.uint8))
     return scene, graph, spd, frames
-
-
-def _bighouse_masks(net, acts, n):
-    """ReLU masks of BigHouseModel's trunk from its activation store [X1 | X2 | X3 | X5]."""
-    sz = [20 * 20 * 32, 9 * 9 * 64, 7 * 7 * 32, 512]
-    assert net.act_floats == sum(sz)
-    shapes = [(n, 20, 20, 32), (n, 9, 9, 64), (n, 7, 7, 32), (n, 512)]
-    out, p = {}, 0
-    for key, s, sh in zip(("m1", "m2", "m3", "m5"), sz, shapes):
-        x = acts[p:p + n * s].view(sh) > 0
-        out[key] = (x.permute(0, 3, 1, 2) if len(sh) == 4 else x).double().cpu()
-        p += n * s
-    return out
-
-
-def _bighouse_forward_masked(ref, image, masks):
-    """BigHouseOracle.features with every ReLU replaced by its given mask -> (x3, f, pre)."""
-    pre = {}
-    pre["z1"] = z1 = ref.conv1(image)
-    pre["z2"] = z2 = ref.conv2(z1 * masks["m1"])
-    pre["z3"] = z3 = ref.conv3(z2 * masks["m2"])
-    x3 = z3 * masks["m3"]
-    pre["z5"] = z5 = ref.fc(x3.flatten(1))
-    return x3, z5 * masks["m5"], pre
-
-
-def _ties_only(masks, pre, pairs):
-    for m, z in pairs.items():
-        zz = pre[z].detach()
-        bad = (masks[m] > 0) != (zz > 0)
-        if bad.any():
-            worst = float(zz[bad].abs().max() / zz.abs().max())
-            assert worst <= 1e-5, "%s: mask disagrees with the oracle's sign at |z| = %.3g of scale" % (m, worst)
 
 
 def _pc_masks(net, params, h_pc):
