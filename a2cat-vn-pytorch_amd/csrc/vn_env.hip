@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "vn_common.h"
+#include "vn_nav.h"
 #include "vn_unit_float.h"
 
 namespace vn {
@@ -89,6 +90,10 @@ struct alignas(128) EnvRec {
   int32_t w[RW_WORDS];
 };
 static_assert(sizeof(EnvRec) == 128, "one record per 128-B line");
+// what the nav kernels (vn_nav.hip) read of a record
+static_assert(NAV_RW_SCENE == RW_ST + ST_SCENE && NAV_RW_STATE == RW_ST + ST_STATE && NAV_RW_GOAL == RW_ST + ST_GOAL &&
+                  NAV_RW_ELAPSED == RW_ST + ST_ELAPSED && NAV_RW_NB == RW_NB && NAV_REC_WORDS == RW_WORDS,
+              "vn_nav.h restates the record layout");
 // A u8 row and an f32 row at one address are different contents: the record tells them apart
 // on the device, so replayed graphs and interleaved vn_step / vn_step_f32 calls stay correct.
 constexpr uint64_t kOutF32 = 1ull << 63;
@@ -1097,6 +1102,8 @@ struct vn_ctx {
   const uint8_t* seg_arena = nullptr;
   int depth_ch = 0, seg_ch = 0;
   AuxRec* arecs = nullptr;
+  // vn_nav_enable: the geodesic tables, the per-env nav record and its outputs (vn_nav.hip)
+  NavState* nav = nullptr;
 };
 
 namespace {
@@ -1144,6 +1151,21 @@ EnvArgs make_args(vn_ctx* c) {
   a.px = c->px;
   a.ch = c->channels;
   return a;
+}
+
+// Navigation info (vn_nav_enable): a step's nav kernel reads done, truncated and ep_length of
+// the step, so where the caller set none the nav state's own arrays stand in and env_kernel
+// writes them as it would a caller's.
+void nav_fill(vn_ctx* c, EnvArgs& a) {
+  if (!c->nav) return;
+  if (!a.done) a.done = c->nav->s_done;
+  if (!a.info_trunc) a.info_trunc = c->nav->s_trunc;
+  if (!a.info_len) a.info_len = c->nav->s_len;
+}
+// After the step's env_kernel launch (rc = its result), on the same stream.
+int nav_after_step(vn_ctx* c, const EnvArgs& a, int rc, hipStream_t stream) {
+  if (rc != VN_OK || !c->nav) return rc;
+  return nav_launch(c->nav, NAV_FORM_STEP, c->recs, a.done, a.info_trunc, a.info_len, stream);
 }
 
 // Whether a launch writing to (obs, goal) may skip rows that already hold their frame. The
@@ -1263,6 +1285,7 @@ void free_ctx(vn_ctx* c) {
                   c->tasks, c->sched, c->flags, c->cur_order, c->cur_count, c->arecs};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
+  nav_destroy(c->nav);
   delete c;
 }
 
@@ -1425,7 +1448,9 @@ int vn_reset(vn_ctx* c, const int32_t* env_mask_dev, vn_stream_t stream) {
   DeviceGuard guard(c->device);
   EnvArgs a = make_args(c);
   a.mask = env_mask_dev;
-  return launch_env<MODE_RESET>(c, a, (hipStream_t)stream);
+  const int rc = launch_env<MODE_RESET>(c, a, (hipStream_t)stream);
+  if (rc != VN_OK || !c->nav) return rc;
+  return nav_launch(c->nav, NAV_FORM_RESET, c->recs, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }
 
 int vn_observe(vn_ctx* c, uint8_t* obs_dev, uint8_t* goal_dev, int32_t* state_dev, vn_stream_t stream) {
@@ -1452,7 +1477,8 @@ int vn_step(vn_ctx* c, const int32_t* actions_dev, uint8_t* obs_dev, uint8_t* go
   a.done = done_dev;
   a.state_out = state_dev;
   a.reuse = take_reuse(c, obs_dev, goal_dev, (hipStream_t)stream);
-  return launch_env<MODE_STEP>(c, a, (hipStream_t)stream);
+  nav_fill(c, a);
+  return nav_after_step(c, a, launch_env<MODE_STEP>(c, a, (hipStream_t)stream), (hipStream_t)stream);
 }
 
 int vn_observe_f32(vn_ctx* c, float* obs_chw_dev, float* goal_chw_dev, int32_t* state_dev, vn_stream_t stream) {
@@ -1483,7 +1509,8 @@ int vn_step_f32(vn_ctx* c, const int32_t* actions_dev, float* obs_chw_dev, float
   a.done = done_dev;
   a.state_out = state_dev;
   a.reuse = take_reuse(c, obs_chw_dev, goal_chw_dev, (hipStream_t)stream);
-  return launch_env_f32<MODE_STEP>(c, a, (hipStream_t)stream);
+  nav_fill(c, a);
+  return nav_after_step(c, a, launch_env_f32<MODE_STEP>(c, a, (hipStream_t)stream), (hipStream_t)stream);
 }
 
 int vn_set_aux_arena(vn_ctx* c, const uint8_t* depth_dev, int depth_channels, const uint8_t* seg_dev,
@@ -1533,7 +1560,9 @@ int vn_step_aux(vn_ctx* c, const int32_t* actions_dev, const vn_obs_set* obs, fl
   a.reward = reward_dev;
   a.done = done_dev;
   a.state_out = state_dev;
-  return launch_env_aux<MODE_STEP>(c, a, obs, "vn_step_aux", (hipStream_t)stream);
+  nav_fill(c, a);
+  return nav_after_step(c, a, launch_env_aux<MODE_STEP>(c, a, obs, "vn_step_aux", (hipStream_t)stream),
+                        (hipStream_t)stream);
 }
 
 int vn_step_a2c(vn_ctx* c, const vn_a2c_step* p, float* reward_dev, uint8_t* done_dev, int32_t* state_dev,
@@ -1559,6 +1588,7 @@ int vn_step_a2c(vn_ctx* c, const vn_a2c_step* p, float* reward_dev, uint8_t* don
   a.lra_next = p->lra_next;
   a.mask_next = p->mask_next;
   a.stats_env = p->episode_stats_env;
+  nav_fill(c, a);
   if (p->head_weight) {
     if (!p->head_bias || !p->head_input || !p->head_out || p->head_out != p->policy_out)
       return fail(VN_EINVAL, "vn_step_a2c: head_weight needs head_bias, head_input and head_out == policy_out");
@@ -1568,9 +1598,91 @@ int vn_step_a2c(vn_ctx* c, const vn_a2c_step* p, float* reward_dev, uint8_t* don
     a.head_b = p->head_bias;
     a.head_x = p->head_input;
     a.head_out = p->head_out;
-    return launch_env<MODE_STEP_HEADS>(c, a, (hipStream_t)stream);
+    return nav_after_step(c, a, launch_env<MODE_STEP_HEADS>(c, a, (hipStream_t)stream), (hipStream_t)stream);
   }
-  return launch_env<MODE_STEP>(c, a, (hipStream_t)stream);
+  return nav_after_step(c, a, launch_env<MODE_STEP>(c, a, (hipStream_t)stream), (hipStream_t)stream);
+}
+
+int vn_nav_enable(vn_ctx* c, int on) {
+  if (!c) return fail(VN_EINVAL, "vn_nav_enable: NULL ctx");
+  std::vector<NavScene> ns(c->n_scenes);
+  for (int k = 0; k < c->n_scenes && on; ++k) {
+    const SceneDev& S = c->scenes_host[k];
+    if (S.n > kNavMaxStates)
+      return fail(VN_EINVAL, "vn_nav_enable: scene " + std::to_string(k) + " has " + std::to_string(S.n) +
+                                 " states, more than " + std::to_string(kNavMaxStates));
+    ns[k] = NavScene{0, S.n, S.graph_off};
+  }
+  DeviceGuard guard(c->device);
+  VN_HIP(hipDeviceSynchronize());
+  nav_destroy(c->nav);
+  c->nav = nullptr;
+  if (!on) return VN_OK;
+  NavState* nav = nullptr;
+  int rc = nav_create(&nav, c->n_envs, ns, c->graph);
+  if (rc != VN_OK) return rc;
+  // every env's record from its current state: a running episode is measured from here
+  rc = nav_launch(nav, NAV_FORM_ENABLE, c->recs, nullptr, nullptr, nullptr, 0);
+  if (rc == VN_OK) {
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) rc = hip_fail(e, "vn_nav_enable: build");
+  }
+  if (rc != VN_OK) {
+    nav_destroy(nav);
+    return rc;
+  }
+  c->nav = nav;
+  return VN_OK;
+}
+
+int vn_set_nav_buffers(vn_ctx* c, int32_t* geo_dist, int32_t* optimal_action, uint8_t* optimal_mask,
+                       uint8_t* ep_success, float* ep_spl, int32_t* ep_start_dist) {
+  if (!c) return fail(VN_EINVAL, "vn_set_nav_buffers: NULL ctx");
+  if (!c->nav) return fail(VN_ESTATE, "vn_set_nav_buffers: navigation info is not enabled (vn_nav_enable)");
+  DeviceGuard guard(c->device);
+  VN_HIP(hipDeviceSynchronize());
+  c->nav->geo_dist = geo_dist;
+  c->nav->opt_action = optimal_action;
+  c->nav->opt_mask = optimal_mask;
+  c->nav->ep_success = ep_success;
+  c->nav->ep_spl = ep_spl;
+  c->nav->ep_start = ep_start_dist;
+  // the new buffers hold the current distance, mask and action at once
+  const int rc = nav_launch(c->nav, NAV_FORM_OUTPUTS, c->recs, nullptr, nullptr, nullptr, 0);
+  if (rc != VN_OK) return rc;
+  VN_HIP(hipDeviceSynchronize());
+  return VN_OK;
+}
+
+int vn_nav_table(vn_ctx* c, int scene, const int16_t** geo_dev, int32_t* n) {
+  if (!c || scene < 0 || scene >= c->n_scenes) return fail(VN_EINVAL, "vn_nav_table: bad args");
+  if (!c->nav) return fail(VN_ESTATE, "vn_nav_table: navigation info is not enabled (vn_nav_enable)");
+  if (geo_dev) *geo_dev = c->nav->geo + c->nav->scenes_host[scene].geo_off;
+  if (n) *n = c->nav->scenes_host[scene].n;
+  return VN_OK;
+}
+
+int vn_get_nav_state(vn_ctx* c, int32_t* dst, vn_stream_t stream) {
+  if (!c || !dst) return fail(VN_EINVAL, "vn_get_nav_state: NULL argument");
+  if (!c->nav) return fail(VN_ESTATE, "vn_get_nav_state: navigation info is not enabled (vn_nav_enable)");
+  DeviceGuard guard(c->device);
+  VN_HIP(hipMemcpyAsync(dst, c->nav->rec, (size_t)c->n_envs * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return VN_OK;
+}
+
+int vn_set_nav_state(vn_ctx* c, const int32_t* src, vn_stream_t stream) {
+  if (!c || !src) return fail(VN_EINVAL, "vn_set_nav_state: NULL argument");
+  if (!c->nav) return fail(VN_ESTATE, "vn_set_nav_state: navigation info is not enabled (vn_nav_enable)");
+  DeviceGuard guard(c->device);
+  VN_HIP(hipMemcpyAsync(c->nav->rec, src, (size_t)c->n_envs * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return VN_OK;
+}
+
+int vn_nav_episode_stats(vn_ctx* c, float* stats4, vn_stream_t stream) {
+  if (!c || !stats4) return fail(VN_EINVAL, "vn_nav_episode_stats: NULL argument");
+  if (!c->nav) return fail(VN_ESTATE, "vn_nav_episode_stats: navigation info is not enabled (vn_nav_enable)");
+  DeviceGuard guard(c->device);
+  return nav_episode_stats(c->nav, stats4, (hipStream_t)stream);
 }
 
 int vn_set_info_buffers(vn_ctx* c, float* ep_return, int32_t* ep_length, int32_t* terminal_state,

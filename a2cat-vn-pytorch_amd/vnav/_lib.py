@@ -140,6 +140,12 @@ SIGNATURES = {
     "vn_set_aux_arena": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int]),
     "vn_observe_aux": (c_int, [c_void_p, P(ObsSet), c_void_p, c_void_p]),
     "vn_step_aux": (c_int, [c_void_p, c_void_p, P(ObsSet), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vn_nav_enable": (c_int, [c_void_p, c_int]),
+    "vn_set_nav_buffers": (c_int, [c_void_p] + [c_void_p] * 6),
+    "vn_nav_table": (c_int, [c_void_p, c_int, P(c_void_p), P(c_int32)]),
+    "vn_get_nav_state": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vn_set_nav_state": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vn_nav_episode_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
 }
 
 SIGNATURES.update({

@@ -67,7 +67,7 @@ class A2CTrainer:
                  aux_weight=0.0, arch="goal", cuda_graph=False, aux_source="rollout", replay_size=8,
                  capture_collectives=False, allreduce_buckets=1, time_collectives=False, dedup_goals=None,
                  unreal=False, pc_weight=0.05, rp_weight=1.0, vr_weight=1.0, pc_gamma=0.9, unreal_envs=16,
-                 unreal_source="rollout"):
+                 unreal_source="rollout", nav_metrics=False):
         self.env = env
         self.lib = _lib.load()
         # check before every replayed UNREAL pass that the side stream's buffers and gradient
@@ -129,6 +129,14 @@ class A2CTrainer:
         self.norm_partial = torch.zeros(512, dtype=torch.float64, **kw)
         self.scalars = torch.zeros(2, dtype=torch.float32, **kw)
         self.episode_stats = torch.zeros(3, dtype=torch.float32, **kw)  # count, return sum, length sum
+        # nav_metrics: success rate and SPL of the finished episodes from the env's navigation
+        # info (vn_nav_enable); nav_stats = [episodes, successes, SPL sum, start-distance sum] of
+        # the last rollout. Episodes already running are measured from here on.
+        self.nav_metrics = bool(nav_metrics)
+        if self.nav_metrics:
+            if not env.nav_info:
+                env.set_nav_info(True)
+            self.nav_stats = torch.zeros(4, dtype=torch.float32, **kw)
         # device schedule: [next sampling-counter base (updates * T), env-steps so far, this
         # update's counter base] and the learning rate of the update (vn_a2c_schedule)
         self.sched = torch.zeros(3, dtype=torch.int64, **kw)
@@ -754,6 +762,8 @@ class A2CTrainer:
             env.step_a2c(self._a2c_steps[t], self.rewards[t], self.dones[t], self.states)
         _lib.check(lib.vn_a2c_episode_stats(_lib.ptr(self.stats_env), E, _lib.ptr(self.episode_stats), self._stream()),
                    "vn_a2c_episode_stats")
+        if self.nav_metrics:
+            env.nav_episode_stats(out=self.nav_stats)
         # bootstrap value of the final observation
         self._bootstrap(self._frames(info["img_row"], info["goal_row"]))
 
@@ -976,6 +986,8 @@ class A2CTrainer:
         vdist.reduce_metrics_(m, 6, self.group)
         if self.unreal and self.world > 1:
             m[9:] /= self.world
+        if self.nav_metrics:  # the four nav sums ride behind, summed over ranks
+            m = torch.cat([m, vdist.reduce_metrics_(self.nav_stats.clone(), 0, self.group)])
         return m
 
     def _graph_update(self):
@@ -1013,6 +1025,11 @@ class A2CTrainer:
         unreal = {}
         if self.unreal:
             unreal = {"pc_loss": vals[9], "rp_loss": vals[10], "vr_loss": vals[11]}
+        nav = {}
+        if self.nav_metrics:
+            n_ep, n_ok, spl_sum, _ = vals[-4:]
+            nav = {"success_rate": n_ok / n_ep if n_ep else float("nan"),
+                   "spl": spl_sum / n_ep if n_ep else float("nan")}
         dt = time.perf_counter() - t0
         return {
             "step": self.total_steps, "updates": self.num_updates,
@@ -1025,6 +1042,7 @@ class A2CTrainer:
             "grad_norm": gnorm, "return_mean": ret_mean, "fps": N * self.world / dt,
             **({"aux_loss": aux_loss} if self.aux_weight > 0 else {}),
             **unreal,
+            **nav,
         }
 
     def run(self, log_every=10, logger=print):
@@ -1039,23 +1057,32 @@ class A2CTrainer:
         actions), no update, until ``episodes`` episodes have finished on all ranks together
         (or ``max_rollouts`` rollouts). The recurrent state carries across rollouts as in
         training; the learning-rate step count is left as it was. Returns the episode count
-        and the mean reward and length of the finished episodes."""
+        and the mean reward and length of the finished episodes; with ``nav_metrics`` also
+        their success rate, mean SPL and mean start distance (geodesic, in actions)."""
         saved_sched = self.sched.clone()  # sampling counter and step count: evaluation leaves both
         E, T = self.env.num_envs, self.num_steps
-        tot = torch.zeros(3, dtype=torch.float64)
+        tot = torch.zeros(7 if self.nav_metrics else 3, dtype=torch.float64)
         for _ in range(int(max_rollouts)):
             self.rollout()
             if self.recurrent:  # (h, c) after the last step carry on, as update() does
                 self._carry_states()
             st = self.episode_stats.to(torch.float64)
+            if self.nav_metrics:
+                st = torch.cat([st, self.nav_stats.to(torch.float64)])
             vdist.reduce_metrics_(st, 0, self.group)
             tot += st.cpu()
             if tot[0] >= episodes:
                 break
         self.sched.copy_(saved_sched)
-        n, rsum, lsum = tot.tolist()
-        return {"episodes": n, "reward": rsum / n if n else float("nan"),
-                "episode_length": lsum / n if n else float("nan")}
+        n, rsum, lsum = tot.tolist()[:3]
+        out = {"episodes": n, "reward": rsum / n if n else float("nan"),
+               "episode_length": lsum / n if n else float("nan")}
+        if self.nav_metrics:
+            n_ep, n_ok, spl_sum, start_sum = tot.tolist()[3:]
+            nan = float("nan")
+            out.update(success_rate=n_ok / n_ep if n_ep else nan, spl=spl_sum / n_ep if n_ep else nan,
+                       start_distance=start_sum / n_ep if n_ep else nan)
+        return out
 
     _RECURRENT_STATE = ("h0", "c0", "prev_action", "prev_reward", "prev_mask")
 
@@ -1067,6 +1094,8 @@ class A2CTrainer:
         if self.recurrent:
             for k in self._RECURRENT_STATE:
                 sd[k] = getattr(self, k).cpu()
+        if self.nav_metrics:  # start distance and length offset of the running episodes
+            sd["env_nav"] = self.env.get_nav_state().cpu()
         if self.replay:  # the replay ring and its draw stream resume exactly
             sd["replay_rows"] = self.replay_rows.cpu()
             sd["replay_meta"] = self.replay_meta.cpu()  # next slot, filled, draw counter, drawn slot
@@ -1109,6 +1138,13 @@ class A2CTrainer:
         self.square_avg.copy_(sd["square_avg"].to(self.device))
         self.env.set_state(sd["env_state"])
         self.env.set_episode_returns(sd["env_ep_return"])
+        if self.nav_metrics:
+            if "env_nav" in sd:
+                self.env.set_nav_state(sd["env_nav"])
+            else:
+                warnings.warn("checkpoint holds no navigation state (saved without nav_metrics): the running "
+                              "episodes are measured from their current positions")
+                self.env.set_nav_info(True)
         self.num_updates = int(sd["num_updates"])
         self.total_steps = int(sd["total_steps"])
         if "sched" in sd:

@@ -17,6 +17,10 @@ that conversion.
 ``aux_observations=True`` (AuxiliaryGraph-v0) makes the observation the reference's five-tuple
 ``(image, goal, depth, segmentation, goal segmentation)``; with the aux frames in the format of
 the image frames all five leave the scene cache in the step's own launch (``vn_step_aux``).
+
+``nav_info=True`` adds the navigation info to every step's ``info``: the geodesic distance to the
+goal on the scene's action graph, the optimal action(s), and per finished episode success, SPL
+and start distance (``vn_nav_enable``; tables built on the device, one small launch per step).
 """
 import ctypes
 import os
@@ -30,6 +34,9 @@ from .scenes import Scene
 OBS_FORMATS = ("u8_hwc", "f32_chw")
 AUX_KEYS = ("depth", "segmentation", "goal_segmentation")
 ST_FIELDS = ("scene", "state", "goal", "obs_state", "elapsed", "episode", "sched_pos")
+# info keys of nav_info=True, in vn_set_nav_buffers' order, with their dtypes
+NAV_KEYS = (("distance_to_goal", torch.int32), ("optimal_action", torch.int32), ("optimal_mask", torch.uint8),
+            ("success", torch.bool), ("spl", torch.float32), ("start_distance", torch.int32))
 
 
 def to_float_chw(frames):
@@ -42,7 +49,7 @@ class VectorEnv:
 
     def __init__(self, scenes, num_envs, seed=0, device=None, max_episode_steps=900, tasks=None,
                  env_scenes=None, autoreset=True, aux_observations=False, reuse_outputs=True,
-                 obs_format="u8_hwc", aux_format=None):
+                 obs_format="u8_hwc", aux_format=None, nav_info=False):
         """obs_format: "u8_hwc" (default) returns and takes uint8 [E,H,W,C] frames; "f32_chw"
         returns and takes float32 [E,C,H,W] frames in [0, 1], every value float(u8) / 255 as
         fp32 division (ScaledFloatFrame's), converted in the step's own launch with the same
@@ -51,7 +58,11 @@ class VectorEnv:
         ``aux_observations=True``. None or "u8_hwc" (default): uint8 [E,H,W,1] / [E,H,W,3] in
         either obs_format; "f32_chw": float32 [E,1,H,W] / [E,3,H,W], only together with
         ``obs_format="f32_chw"``. When both formats are equal the five frames are written by one
-        launch (vn_step_aux) and ``out=`` may carry the three aux buffers (``step``)."""
+        launch (vn_step_aux) and ``out=`` may carry the three aux buffers (``step``).
+        nav_info: every step's info also carries ``distance_to_goal`` (least number of actions
+        to the goal on the scene's action graph, -1 = unreachable), ``optimal_action`` /
+        ``optimal_mask`` (a / all first actions of a shortest path, -1 / 0 if none), and the
+        episode's ``success``, ``spl`` and ``start_distance``."""
         if obs_format not in OBS_FORMATS:
             raise ValueError("obs_format must be one of %s, got %r" % (OBS_FORMATS, obs_format))
         if aux_format is not None and aux_format not in OBS_FORMATS:
@@ -102,6 +113,7 @@ class VectorEnv:
                                           ctypes.c_uint64(self.seed & (2**64 - 1)),
                                           self.device.index, ctypes.byref(handle)), "vn_create")
         self._ctx = handle
+        self.nav_info = False
         # bumped by every call that replaces the kernels' per-ctx configuration (tables,
         # schedules, limits): a captured hipGraph holds the old launch arguments and must be
         # recaptured (A2CTrainer checks it before each replay)
@@ -151,6 +163,8 @@ class VectorEnv:
             dc, sc = int(self.aux_arena[0].shape[3]), int(self.aux_arena[1].shape[3])
             chw = self.aux_format == "f32_chw"
             self.aux_shapes = tuple((c, H, W) if chw else (H, W, c) for c in (dc, sc, sc))
+        if nav_info:
+            self.set_nav_info(True)
 
     def _build_aux_arena(self):
         """Depth [rows,H,W,1] and segmentation [rows,H,W,3] uint8 on the device, indexed by
@@ -180,6 +194,87 @@ class VectorEnv:
                                                self._stream()), "vn_gather_rows")
             out.append(dst)
         return tuple(out)
+
+    # -- navigation info -----------------------------------------------------
+    def set_nav_info(self, on, buffers=None):
+        """Enable / disable the navigation info (vn_nav_enable): builds the scenes' geodesic
+        tables on the device and adds NAV_KEYS to info. Episodes already running are measured
+        from here. ``buffers``: the caller's own [E] output tensors in NAV_KEYS' order (any may
+        be None: not written), e.g. a trainer's rollout slots; default the env's own."""
+        if on:
+            if buffers is None:
+                buffers = [torch.zeros(self.num_envs, dtype=dt, device=self.device) for _, dt in NAV_KEYS]
+            buffers = list(buffers)
+            if len(buffers) != len(NAV_KEYS):
+                raise ValueError("nav buffers: one per key of %s" % ([k for k, _ in NAV_KEYS],))
+            for (k, dt), t in zip(NAV_KEYS, buffers):
+                self._check_out(k, t, dt, self.num_envs)
+        self.config_generation += 1
+        for k, _ in NAV_KEYS:
+            self._info.pop(k, None)
+        self.nav_info = False
+        _lib.check(self.lib.vn_nav_enable(self._ctx, 1 if on else 0), "vn_nav_enable")
+        if not on:
+            return
+        torch.cuda.synchronize(self.device)  # the buffers' zero fill precedes the call's own write
+        _lib.check(self.lib.vn_set_nav_buffers(self._ctx, *[_lib.ptr(t) for t in buffers]), "vn_set_nav_buffers")
+        self.nav_info = True
+        for (k, _), t in zip(NAV_KEYS, buffers):
+            if t is not None:
+                self._info[k] = t
+
+    def nav_outputs(self):
+        """The env's own navigation buffers by info key (no copies): after reset() the first
+        three hold the new episodes' values, after a step all six hold the step's."""
+        self._need_nav()
+        return {k: self._info[k] for k, _ in NAV_KEYS if k in self._info}
+
+    def _need_nav(self):
+        if not self.nav_info:
+            raise _lib.VnavError("navigation info is off: VectorEnv(..., nav_info=True)")
+
+    def geodesic(self, scene_index):
+        """The scene's action-graph geodesic table: int16 [N, N] device tensor indexed
+        [goal, state] (a copy; -1 = the goal cannot be reached from the state)."""
+        self._need_nav()
+        p, n = ctypes.c_void_p(), ctypes.c_int32()
+        _lib.check(self.lib.vn_nav_table(self._ctx, int(scene_index), ctypes.byref(p), ctypes.byref(n)),
+                   "vn_nav_table")
+        out = torch.empty((n.value, n.value), dtype=torch.int16, device=self.device)
+        rows = torch.arange(n.value, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.vn_gather_rows(p, 2 * n.value, _lib.ptr(rows), n.value, _lib.ptr(out), self._stream()),
+                   "vn_gather_rows")
+        rows.record_stream(torch.cuda.current_stream(self.device))
+        return out
+
+    def nav_episode_stats(self, out=None):
+        """float32 [4]: finished episodes, successes, SPL sum, start-distance sum over all envs
+        since the last call (vn_nav_episode_stats: fixed-order sums, then zeroed)."""
+        self._need_nav()
+        if out is None:
+            out = torch.empty(4, dtype=torch.float32, device=self.device)
+        else:
+            self._check_out("nav stats", out, torch.float32, 4)
+        _lib.check(self.lib.vn_nav_episode_stats(self._ctx, _lib.ptr(out), self._stream()), "vn_nav_episode_stats")
+        return out
+
+    def get_nav_state(self):
+        """The nav record a checkpoint needs: int32 [2, E] (start distance, length offset)."""
+        self._need_nav()
+        buf = torch.empty((2, self.num_envs), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.vn_get_nav_state(self._ctx, _lib.ptr(buf), self._stream()), "vn_get_nav_state")
+        return buf
+
+    def set_nav_state(self, buf):
+        """Restore get_nav_state()'s table; call it right after set_state()."""
+        self._need_nav()
+        buf = torch.as_tensor(buf)
+        if tuple(buf.shape) != (2, self.num_envs):
+            raise ValueError("nav state must be [2, %d] (this env), got %s" % (self.num_envs, tuple(buf.shape)))
+        buf = buf.to(device=self.device, dtype=torch.int32).contiguous()
+        _lib.check(self.lib.vn_set_nav_state(self._ctx, _lib.ptr(buf), self._stream()), "vn_set_nav_state")
+        # the copy is stream-ordered: keep the source alive until it has run
+        buf.record_stream(torch.cuda.current_stream(self.device))
 
     # -- configuration -------------------------------------------------------
     def set_max_episode_steps(self, n):
@@ -604,9 +699,9 @@ class CachedThorEnv:
     offline with tools/h5_to_npz.py --size). Every call synchronises with the device; the
     batched ``VectorEnv`` is the fast path."""
 
-    def __init__(self, scene, seed=0, device=None, max_episode_steps=900, float_frames=True):
+    def __init__(self, scene, seed=0, device=None, max_episode_steps=900, float_frames=True, nav_info=False):
         self._env = VectorEnv([scene], 1, seed=seed, device=device, max_episode_steps=max_episode_steps,
-                              autoreset=False)
+                              autoreset=False, nav_info=nav_info)
         self.float_frames = bool(float_frames)
         self.action_size = VectorEnv.num_actions  # get_action_size (cached.py:66-68)
         self.max_episode_steps = max_episode_steps
@@ -625,6 +720,9 @@ class CachedThorEnv:
         info_out = {}
         if bool(info["truncated"][0].item()):
             info_out["TimeLimit.truncated"] = True  # gym's TimeLimit (environments/gym_ai2thor/__init__.py:48)
+        for k, _ in NAV_KEYS:  # nav_info=True: the navigation keys as Python scalars
+            if k in info:
+                info_out[k] = info[k][0].item()
         return self._obs(img, goal), float(reward[0].item()), bool(done[0].item()), info_out
 
     @property

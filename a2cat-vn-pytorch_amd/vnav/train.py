@@ -111,6 +111,8 @@ class Experiment:
     rp_weight = 1.0
     pc_weight = 0.05
     vr_weight = 1.0
+    # success rate and SPL of the finished episodes (A2CTrainer nav_metrics; test() turns it on)
+    nav_metrics = False
 
     def __init__(self, env_kwargs=None, model_kwargs=None, save_dir=None, seed=0, device=None, logger=print,
                  **overrides):
@@ -148,7 +150,7 @@ class Experiment:
                           vr_weight=self.vr_weight, unreal_source=self.unreal_source,
                           # world > 1: only on explicit opt-in (the captured RCCL path is unvalidated)
                           cuda_graph=self.cuda_graph and (self.world == 1 or self.capture_collectives),
-                          capture_collectives=self.capture_collectives)
+                          capture_collectives=self.capture_collectives, nav_metrics=self.nav_metrics)
 
     def _setup(self):
         if self.trainer is None:
@@ -287,7 +289,7 @@ class Experiment:
         if resume and self._resume_decision():
             self.load_checkpoint()
         tr = self._setup()
-        window = dict(episodes=0.0, rsum=0.0, lsum=0.0)
+        window = dict(episodes=0.0, rsum=0.0, lsum=0.0, ok=0.0, spl=0.0)
         last = None
         next_save = (tr.total_steps // self.saving_period + 1) * self.saving_period if self.saving_period else None
         t0, s0 = time.perf_counter(), tr.total_steps
@@ -298,6 +300,9 @@ class Experiment:
                 window["episodes"] += m["episodes"]
                 window["rsum"] += m["reward"] * m["episodes"]
                 window["lsum"] += m["episode_length"] * m["episodes"]
+                if "spl" in m:
+                    window["ok"] += m["success_rate"] * m["episodes"]
+                    window["spl"] += m["spl"] * m["episodes"]
             if self.episode_log_interval and window["episodes"] >= self.episode_log_interval:
                 now = time.perf_counter()
                 row = {k: m[k] for k in ("step", "updates", "value_loss", "action_loss", "entropy", "loss")}
@@ -306,8 +311,10 @@ class Experiment:
                 row.update(episodes=int(window["episodes"]), reward=window["rsum"] / window["episodes"],
                            episode_length=window["lsum"] / window["episodes"],
                            fps=int((tr.total_steps - s0) / max(now - t0, 1e-9)))
+                if "spl" in m:
+                    row.update(success_rate=window["ok"] / window["episodes"], spl=window["spl"] / window["episodes"])
                 self._log(row)
-                window = dict(episodes=0.0, rsum=0.0, lsum=0.0)
+                window = dict(episodes=0.0, rsum=0.0, lsum=0.0, ok=0.0, spl=0.0)
                 t0, s0 = now, tr.total_steps
             if self.save and next_save is not None and tr.total_steps >= next_save:
                 self._saving(self.save_checkpoint())
@@ -325,11 +332,14 @@ class Experiment:
         (default validation_episodes, else 100) episodes. Reads save_dir/checkpoint.pt (or
         ``checkpoint``), whichever world wrote it: the policy parameters are world-agnostic,
         a single-process file also restores its env state. Raises FileNotFoundError when
-        there is no checkpoint (evaluating untrained weights would be silent nonsense)."""
+        there is no checkpoint (evaluating untrained weights would be silent nonsense). The
+        result also carries the episodes' success rate, mean SPL and mean start distance."""
         path = checkpoint or self.checkpoint_path
         if not os.path.exists(path):
             raise FileNotFoundError("no checkpoint to test: %s (train first, or pass checkpoint=)" % path)
         sd = torch.load(path, map_location="cpu", weights_only=True)
+        if self.trainer is None:
+            self.nav_metrics = True
         tr = self._setup()
         if sd.get("params_only") or (int(sd.get("world", 1)), int(sd.get("rank", 0))) != (self.world, self.rank):
             tr.load_params_state_dict(sd)
@@ -437,6 +447,8 @@ def main(argv=None):
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--cuda-graph", action="store_true", help="replay each update as a captured hipGraph (1 GPU)")
     p.add_argument("--resume", action="store_true", help="continue from the checkpoint in --save-dir")
+    p.add_argument("--nav-metrics", action="store_true",
+                   help="log success_rate and spl of the finished episodes while training (--test always does)")
     a = p.parse_args(argv)
     vdist.init_distributed()
     env_kwargs = {}
@@ -452,6 +464,8 @@ def main(argv=None):
         over["max_time_steps"] = a.max_time_steps
     if a.cuda_graph:
         over["cuda_graph"] = True
+    if a.nav_metrics:
+        over["nav_metrics"] = True
     exp = make_trainer(a.name, env_kwargs=env_kwargs, save_dir=a.save_dir, seed=a.seed, **over)
     if a.test:
         exp.test(episodes=a.episodes)

@@ -296,6 +296,50 @@ int vn_set_state(vn_ctx* ctx, const int32_t* src_dev_7xE, vn_stream_t stream);
 int vn_get_episode_returns(vn_ctx* ctx, float* dst_dev_E, vn_stream_t stream);
 int vn_set_episode_returns(vn_ctx* ctx, const float* src_dev_E, vn_stream_t stream);
 
+/* Navigation info: geodesic distance to the goal, optimal action, success and SPL per env.
+ * on = 1 builds, per scene and on the device, the action-graph geodesic table geo[g][s]: the
+ * least number of actions that lead from state s to state g along graph[.][0..3] (-1 = no
+ * edge); 0 for s == g, -1 where g cannot be reached. int16, goal-major. This is not the
+ * scene's spd table, which ranks start states for the sampler and counts no rotations in
+ * place. It also allocates the per-env nav record (start distance, length offset) and the
+ * per-env accumulators, and starts every env's record from its current state: an env with
+ * elapsed > 0 is measured from here (start distance = its current distance, length offset =
+ * elapsed); every later episode has offset 0. A scene of more than 16384 states returns
+ * VN_EINVAL and enables nothing. on = 0 frees everything. Replaces launch arguments like the
+ * vn_set_* calls: synchronises, and a captured graph must be recaptured.
+ * While enabled, vn_step / vn_step_f32 / vn_step_aux / vn_step_a2c launch one more small kernel
+ * on the caller's stream after the step's own, vn_reset a refresh form of it (distance, mask,
+ * action and the start record of the envs it reset; it counts nothing). vn_set_state leaves the
+ * nav record alone: restore it with vn_set_nav_state right after; the next step recomputes
+ * distance, mask and action. */
+int vn_nav_enable(vn_ctx* ctx, int on);
+/* Persistent [n_envs] device outputs, written for every env by every step (any may be NULL):
+ *   geo_dist: geo[goal][state] of the state the step leaves the env in (after an auto-reset
+ *     the new episode's state and goal);
+ *   optimal_mask: bit a set iff graph[state][a] != -1, geo_dist > 0 and
+ *     geo[goal][graph[state][a]] == geo_dist - 1; 0 on the goal and where it is unreachable;
+ *   optimal_action: lowest set bit of the mask, -1 if the mask is 0;
+ *   ep_start_dist: geodesic distance at the start of the episode this step belonged to (the
+ *     finished episode where done, never the new one);
+ *   ep_success: done && !truncated (reaching the goal exactly at the time limit succeeds);
+ *   ep_spl: 0 unless ep_success; then, with l = ep_start_dist and p = the finished episode's
+ *     length minus the length offset, (float)l / (float)max(p, l), one fp32 division; 1 when
+ *     l == 0, 0 when l < 0.
+ * The call also writes the current geo_dist / optimal_mask / optimal_action into the new
+ * buffers. VN_ESTATE before vn_nav_enable. Synchronises. */
+int vn_set_nav_buffers(vn_ctx* ctx, int32_t* geo_dist, int32_t* optimal_action, uint8_t* optimal_mask,
+                       uint8_t* ep_success, float* ep_spl, int32_t* ep_start_dist);
+/* The scene's [n][n] int16 table on the device, indexed [goal][state]. */
+int vn_nav_table(vn_ctx* ctx, int scene, const int16_t** geo_dev, int32_t* n);
+/* The part of the nav record a checkpoint needs, [2][n_envs] int32 on the device: start
+ * distance, length offset. Stream-ordered copies. */
+int vn_get_nav_state(vn_ctx* ctx, int32_t* dst_dev_2xE, vn_stream_t stream);
+int vn_set_nav_state(vn_ctx* ctx, const int32_t* src_dev_2xE, vn_stream_t stream);
+/* stats4 (device) = fixed-order sums over envs of the per-env accumulators: finished
+ * episodes, successes, SPL sum, start-distance sum (an unreachable start adds its -1); the
+ * accumulators are then zeroed. Same inputs, same bits. No host argument: capturable. */
+int vn_nav_episode_stats(vn_ctx* ctx, float* stats4_dev, vn_stream_t stream);
+
 /* Scene-cache arena: all scenes' frames back to back, row = frame. */
 int vn_frame_arena(vn_ctx* ctx, const uint8_t** arena_dev, int64_t* frame_bytes,
                    int64_t* n_rows);
