@@ -27,5 +27,8 @@ Modules
   few_env_cases.py  case tables and inputs of the few-env / float-frame / 1..7-action tests
   unreal_head_cases.py  case tables of the UNREAL head tests and the launch rules (split-K,
               weight-gradient slabs, reduce lanes, colsum blocks) that place them
+  aux_head_cases.py  case tables of the aux deconv head tests, the launch rules (samples per
+              item, bands, persistent grids, the finish kernel's lanes, the two-stage reduce) that
+              place them, seeded inputs and the float64 restatement of the heads and their checks
   update_checks.py  one A2CTrainer update restated in float64, the UNREAL terms included
 """
