@@ -5,7 +5,8 @@ env.step (VectorEnv, libvnav.so) and the A2C rollout/update of the goal-conditio
 CNN policy. See DESIGN.md at the repository root.
 """
 from .scenes import (Scene, grid_tables, load_graph_pickle, load_h5, load_npz, maze_scene, oriented_scene,  # noqa: F401
-                     oriented_tables, scene_from_arrays, synthetic_scene)
+                     oriented_tables, resize_frames, resize_scene, resize_taps, scene_from_arrays,
+                     synthetic_scene)
 from .envs import CachedThorEnv, VectorEnv, make, to_float_chw  # noqa: F401
 from .policy import BigHousePolicy, GoalNavPolicy, PolicyNet  # noqa: F401
 from .a2c import A2CTrainer  # noqa: F401

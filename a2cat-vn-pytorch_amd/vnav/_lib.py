@@ -136,6 +136,8 @@ SIGNATURES = {
     "vn_error_flags_sync": (c_int, [c_void_p, P(c_uint32), c_int]),
     "vn_num_envs": (c_int, [c_void_p]),
     "vn_gather_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
+    "vn_resize_frames": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, P(c_double), c_int,
+                                 P(c_double), c_int, c_void_p, c_void_p]),
     "vn_step_a2c": (c_int, [c_void_p, P(A2CStep), c_void_p, c_void_p, c_void_p, c_void_p]),
     "vn_set_aux_arena": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int]),
     "vn_observe_aux": (c_int, [c_void_p, P(ObsSet), c_void_p, c_void_p]),

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .scenes import Scene
+from .scenes import Scene, resize_scene
 
 OBS_FORMATS = ("u8_hwc", "f32_chw")
 AUX_KEYS = ("depth", "segmentation", "goal_segmentation")
@@ -49,7 +49,7 @@ class VectorEnv:
 
     def __init__(self, scenes, num_envs, seed=0, device=None, max_episode_steps=900, tasks=None,
                  env_scenes=None, autoreset=True, aux_observations=False, reuse_outputs=True,
-                 obs_format="u8_hwc", aux_format=None, nav_info=False):
+                 obs_format="u8_hwc", aux_format=None, nav_info=False, image_size=None):
         """obs_format: "u8_hwc" (default) returns and takes uint8 [E,H,W,C] frames; "f32_chw"
         returns and takes float32 [E,C,H,W] frames in [0, 1], every value float(u8) / 255 as
         fp32 division (ScaledFloatFrame's), converted in the step's own launch with the same
@@ -62,7 +62,11 @@ class VectorEnv:
         nav_info: every step's info also carries ``distance_to_goal`` (least number of actions
         to the goal on the scene's action graph, -1 = unreachable), ``optimal_action`` /
         ``optimal_mask`` (a / all first actions of a shortest path, -1 / 0 if none), and the
-        episode's ``success``, ``spl`` and ``start_distance``."""
+        episode's ``success``, ``spl`` and ``start_distance``.
+        image_size: (height, width) of the frames the env emits, the reference cached env's
+        ``image_size`` (cached.py:19,62-64). Every scene whose frames have another size is
+        resized on the device before the scene cache is built (``scenes.resize_scene``); None
+        (default) and scenes already of that size are left untouched."""
         if obs_format not in OBS_FORMATS:
             raise ValueError("obs_format must be one of %s, got %r" % (OBS_FORMATS, obs_format))
         if aux_format is not None and aux_format not in OBS_FORMATS:
@@ -79,6 +83,10 @@ class VectorEnv:
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else
                                    torch.device(device).index or 0)
         self.scenes = list(scenes)
+        if image_size is not None:
+            hw = tuple(int(v) for v in image_size)
+            self.scenes = [s if tuple(s.frame_shape[:2]) == hw else resize_scene(s, hw, device=self.device)
+                           for s in self.scenes]
         self.num_envs = int(num_envs)
         self.seed = int(seed)
         self.frame_shape = tuple(self.scenes[0].frame_shape)
@@ -695,13 +703,15 @@ class CachedThorEnv:
     test-time episodes). ``reset() -> (image, goal)``; ``step(a) -> (obs, reward, done,
     info)`` with no auto-reset: on a terminal step the previous observation is returned
     (cached.py:90-96) and the caller resets, as with the reference. Frames are float64 in
-    [0, 1], HWC, as ``_preprocess_frame`` returns at equal size (cached.py:62-64; resize
-    offline with tools/h5_to_npz.py --size). Every call synchronises with the device; the
-    batched ``VectorEnv`` is the fast path."""
+    [0, 1], HWC, as ``_preprocess_frame`` returns (cached.py:62-64): at the scene's own size,
+    or with ``image_size=(H, W)`` resized once on the device when the env is built, each value
+    then byte / 255 with the byte round(255 x) of the reference's float x. Every call
+    synchronises with the device; the batched ``VectorEnv`` is the fast path."""
 
-    def __init__(self, scene, seed=0, device=None, max_episode_steps=900, float_frames=True, nav_info=False):
+    def __init__(self, scene, seed=0, device=None, max_episode_steps=900, float_frames=True, nav_info=False,
+                 image_size=None):
         self._env = VectorEnv([scene], 1, seed=seed, device=device, max_episode_steps=max_episode_steps,
-                              autoreset=False, nav_info=nav_info)
+                              autoreset=False, nav_info=nav_info, image_size=image_size)
         self.float_frames = bool(float_frames)
         self.action_size = VectorEnv.num_actions  # get_action_size (cached.py:66-68)
         self.max_episode_steps = max_episode_steps

@@ -20,7 +20,15 @@ Builders
                             37-75) through an allow-list unpickler -> oriented_scene
   scene_from_arrays(...)    h5 datasets already in memory; load_h5 / load_npz read them
                             (tools/h5_to_npz.py converts + optionally resizes offline)
+
+Resize (the reference's ``image_size``, cached.py:19,62-64), on the device
+  resize_taps(n, no)        the anti-aliasing Gaussian of one axis
+  resize_frames(frames, image_size)   uint8 [N,H,W,C] -> [N,Ho,Wo,C] (vn_resize_frames)
+  resize_scene(scene, image_size)     a scene with every frame set resized
+  load_npz / load_h5 (..., image_size=)   and VectorEnv / make / CachedThorEnv likewise
 """
+import ctypes
+import dataclasses
 import io
 import pickle
 from dataclasses import dataclass, field
@@ -197,24 +205,114 @@ def scene_from_arrays(graph, spd, observations, rewards=CACHED_REWARDS, name="")
                  rewards=rewards, terminal_obs=0, name=name)
 
 
-def load_npz(path, name=None):
-    """A scene converted from a reference h5 file by tools/h5_to_npz.py."""
+# bytes of source frames resident on the device per resize_frames chunk (a scene of 1500
+# frames at 300x400x3 is 540 MB: it streams through in three chunks)
+RESIZE_CHUNK_BYTES = 256 << 20
+
+
+def resize_taps(n, no):
+    """(sigma, R, taps) of the reference's anti-aliasing Gaussian along an axis resized from n
+    to no samples: sigma = max(0, (n / no - 1) / 2) (skimage.transform.resize), R =
+    int(4 sigma + 0.5) and the 2R+1 weights exp(-0.5 / sigma^2 k^2) / sum in fp64
+    (scipy.ndimage's kernel). taps is None where sigma <= 1e-15: the axis is not filtered."""
+    sigma = max(0.0, (n / no - 1) / 2)
+    if sigma <= 1e-15:
+        return sigma, 0, None
+    R = int(4.0 * sigma + 0.5)
+    k = np.arange(-R, R + 1)
+    w = np.exp(-0.5 / (sigma * sigma) * k ** 2)
+    return sigma, R, w / w.sum()
+
+
+def _image_size(image_size):
+    hw = tuple(int(v) for v in image_size)
+    if len(hw) != 2:
+        raise ValueError("image_size must be (height, width), got %r" % (image_size,))
+    return hw
+
+
+def resize_frames(frames, image_size, device=None, chunk_frames=None):
+    """uint8 frames [N,H,W,C] -> numpy uint8 [N,Ho,Wo,C] by the reference's
+    skimage.transform.resize(frame, image_size, anti_aliasing=True) (cached.py:62-64) stored as
+    round(255 x): Gaussian on the uint8 image with a floor after each axis, bilinear sampling,
+    ties to even (DESIGN.md "Scene ingest: resize on the device"). Runs on the GPU
+    (vn_resize_frames): the frames are uploaded in chunks of chunk_frames (default: as many as
+    fit RESIZE_CHUNK_BYTES) and each chunk is resized by one call. Raises VnavError without a
+    GPU: there is no CPU fallback. Only shrinking (Ho <= H, Wo <= W) and C in (1, 3)."""
+    import torch
+
+    from . import _lib
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    if frames.ndim != 4:
+        raise ValueError("frames must be [N,H,W,C], got shape %s" % (frames.shape,))
+    oh, ow = _image_size(image_size)
+    n, h, w, c = frames.shape
+    if not torch.cuda.is_available():
+        raise _lib.VnavError("resize_frames requires a ROCm GPU (no CPU fallback)")
+    lib = _lib.load()
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else torch.device(device).index or 0)
+    out = np.empty((n, oh, ow, c), dtype=np.uint8)
+    if n == 0:
+        return out
+    _, rr, tr = resize_taps(h, oh) if oh <= h else (0.0, 0, None)
+    _, rc, tc = resize_taps(w, ow) if ow <= w else (0.0, 0, None)
+
+    def as_ptr(t):
+        return None if t is None else t.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+    if chunk_frames is None:
+        chunk_frames = max(1, RESIZE_CHUNK_BYTES // max(1, h * w * c))
+    chunk_frames = max(1, int(chunk_frames))
+    with torch.cuda.device(dev):
+        for k in range(0, n, chunk_frames):
+            src = torch.from_numpy(frames[k:k + chunk_frames]).to(dev)
+            dst = torch.empty((src.shape[0], oh, ow, c), dtype=torch.uint8, device=dev)
+            _lib.check(lib.vn_resize_frames(_lib.ptr(src), src.shape[0], h, w, c, oh, ow, as_ptr(tr), rr, as_ptr(tc),
+                                            rc, _lib.ptr(dst), _lib.stream_ptr(dev)), "vn_resize_frames")
+            out[k:k + chunk_frames] = dst.cpu().numpy()
+    return out
+
+
+def resize_scene(scene, image_size, device=None):
+    """A new Scene whose frames are image_size: ``observations``, ``companion``, ``depth`` and
+    ``segmentation`` all go through resize_frames, ``frame_shape`` follows, the tables (graph,
+    spd, goals, ...) are shared with ``scene``. Resizing depth and segmentation by the image's
+    rule is this engine's choice: the reference's cached env resizes only the rgb frame it emits
+    and has no depth or segmentation there (anti-aliased, interpolated labels are not labels;
+    keep the scene's own size where exact class ids matter). A scene already of image_size is
+    returned as it is; one with synthetic frames (``observations=None``) raises ValueError."""
+    hw = _image_size(image_size)
+    if scene.observations is None:
+        raise ValueError("scene %r has synthetic frames (observations=None): nothing to resize; "
+                         "build it at the wanted frame_shape" % (scene.name,))
+    if tuple(scene.frame_shape[:2]) == hw:
+        return scene
+    new = {k: resize_frames(getattr(scene, k), hw, device=device)
+           for k in ("observations", "companion", "depth", "segmentation") if getattr(scene, k) is not None}
+    return dataclasses.replace(scene, frame_shape=hw + (int(scene.frame_shape[2]),), **new)
+
+
+def load_npz(path, name=None, image_size=None):
+    """A scene converted from a reference h5 file by tools/h5_to_npz.py. image_size=(H, W)
+    resizes the frames on the device (resize_scene), as the reference's cached env does."""
     d = np.load(path, allow_pickle=False)
-    return scene_from_arrays(d["graph"], d["shortest_path_distance"], d["observation"],
-                             name=name or path)
+    scene = scene_from_arrays(d["graph"], d["shortest_path_distance"], d["observation"], name=name or path)
+    return scene if image_size is None else resize_scene(scene, image_size)
 
 
-def load_h5(path, name=None):
+def load_h5(path, name=None, image_size=None):
     """A reference h5 scene (graph/util.py:222-227 layout; read as cached.py:26-32). Needs
-    h5py; without it convert offline with tools/h5_to_npz.py and use load_npz."""
+    h5py; without it convert offline with tools/h5_to_npz.py and use load_npz. image_size as
+    for load_npz."""
     try:
         import h5py
     except ImportError as e:
         raise ImportError("h5py is not importable here: convert %s with tools/h5_to_npz.py "
                           "(/opt/conda/bin/python3.9) and load the .npz" % path) from e
     with h5py.File(path, "r") as f:
-        return scene_from_arrays(f["graph"][()], f["shortest_path_distance"][()], f["observation"][()],
-                                 name=name or path)
+        scene = scene_from_arrays(f["graph"][()], f["shortest_path_distance"][()], f["observation"][()],
+                                  name=name or path)
+    return scene if image_size is None else resize_scene(scene, image_size)
 
 
 def oriented_tables(maze):

@@ -6,6 +6,7 @@ driven by experiments/thor_cached_auxiliary.py:26-84).
     python -m vnav.train thor-cached-auxiliary [--scene thor-cached-212-174.pkl] [--save-dir D]
     python -m vnav.train thor-cached-auxiliary --test [--episodes 100]      # test-train.py
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m vnav.train cached-thor --envs 4096
+    python -m vnav.train cached-thor --scene dump-300x400.npz --image-size 84 84   # resized on the device
 
 An experiment is a class registered under its name with the deep_rl trainer arguments
 (max_time_steps, validation_period, validation_episodes, episode_log_interval,
@@ -413,7 +414,8 @@ class ThorCachedAuxiliary(Experiment):
             scene = _synthetic_oriented(tuple(kwargs.get("grid", (16, 16))), tuple(kwargs.get("frame", (174, 174))),
                                         goal, seed=kwargs.get("scene_seed", 0))
         return VectorEnv([scene], kwargs.get("num_envs", self.num_processes),
-                         seed=vdist.rank_seed(self.seed + 1, self.rank), device=self.device, max_episode_steps=900)
+                         seed=vdist.rank_seed(self.seed + 1, self.rank), device=self.device, max_episode_steps=900,
+                         image_size=kwargs.get("image_size"))
 
 
 @register_trainer("cached-thor", max_time_steps=1e9, validation_period=None, validation_episodes=None,
@@ -432,7 +434,8 @@ class CachedThor(Experiment):
         else:
             scenes = [synthetic_scene(k) for k in range(int(kwargs.get("n_scenes", 20)))]
         return VectorEnv(scenes, kwargs.get("num_envs", self.num_processes),
-                         seed=vdist.rank_seed(self.seed + 1, self.rank), device=self.device, max_episode_steps=900)
+                         seed=vdist.rank_seed(self.seed + 1, self.rank), device=self.device, max_episode_steps=900,
+                         image_size=kwargs.get("image_size") if paths else None)
 
 
 def main(argv=None):
@@ -440,6 +443,8 @@ def main(argv=None):
     p.add_argument("name", help="experiment name (%s)" % ", ".join(registered()))
     p.add_argument("--test", action="store_true", help="test-train.py: evaluate the saved policy")
     p.add_argument("--scene", action="append", default=[], help="scene file(s): .pkl (ThorGridWorld), .h5 or .npz")
+    p.add_argument("--image-size", type=int, nargs=2, metavar=("H", "W"), default=None,
+                   help="resize the frames of the --scene files on the device (the cached env's image_size)")
     p.add_argument("--envs", type=int, default=None, help="envs per GPU (default: the experiment's num_processes)")
     p.add_argument("--max-time-steps", type=float, default=None)
     p.add_argument("--save-dir", default=None)
@@ -459,6 +464,8 @@ def main(argv=None):
             env_kwargs["scene"] = a.scene[0]
         else:
             env_kwargs["scenes"] = a.scene
+        if a.image_size:
+            env_kwargs["image_size"] = tuple(a.image_size)
     over = {}
     if a.max_time_steps is not None:
         over["max_time_steps"] = a.max_time_steps

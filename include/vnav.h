@@ -282,6 +282,35 @@ int vn_random_actions(vn_ctx* ctx, int32_t* actions_dev, uint64_t step, vn_strea
 int vn_gather_rows(const uint8_t* src_dev, int64_t row_bytes, const int32_t* rows_dev, int n, uint8_t* dst_dev,
                    vn_stream_t stream);
 
+/* Scene ingest: resize n packed uint8 frames [n][h][w][c] -> [n][oh][ow][c] on the device, as
+ * the reference's cached env does per emitted frame (skimage.transform.resize(frame,
+ * image_size, anti_aliasing=True), environments/gym_ai2thor/envs/cached.py:62-64), stored as
+ * round(255 x) bytes. Per output byte, in this order (DESIGN.md "Scene ingest: resize on the
+ * device"):
+ *   1. Gaussian along the rows axis on the uint8 input, fp64 without contraction, in scipy's
+ *      symmetric order acc = x[i] w[R]; acc += (x[i+j] + x[i-j]) w[j+R] for j = -R..-1; the
+ *      result is floored to a byte. The border mirrors without repeating the edge sample
+ *      (period 2 (n - 1), any number of reflections; n = 1: always sample 0);
+ *   2. the same along the columns axis on those bytes, floored to a byte again;
+ *   3. bilinear sampling at r = (i + 0.5) h / oh - 0.5, c = (j + 0.5) w / ow - 0.5 in 64-bit
+ *      integers: S / D with D = 4 oh ow, rounded to nearest, ties to even.
+ * taps_*_host: the axis's 2R+1 normalised weights on the host, fp64, w[k + R] for k = -R..R
+ * (vnav.scenes.resize_taps); they are read before the call returns and travel in the launch
+ * arguments, so their bits are the caller's and the call allocates and copies nothing. Only
+ * w[0..R] enter the sum (the symmetric form). NULL with radius 0 skips the axis's pass.
+ * oh == h && ow == w is a plain device-to-device copy. Stream-ordered on the current device; src
+ * and dst need no alignment and must not overlap.
+ * VN_EINVAL, with nothing written: NULL frames; n, a size or a channel count <= 0; c not 1 or 3;
+ * oh > h or ow > w (upsampling would need the warp's border rule); a radius outside
+ * 0..VN_RESIZE_MAX_RADIUS (32 covers every factor up to 17 per axis: R = int(2 (f - 1) + 0.5));
+ * NULL taps with a radius > 0; w * c > VN_RESIZE_MAX_ROW_BYTES (two filtered rows must fit
+ * the workgroup's LDS). */
+#define VN_RESIZE_MAX_RADIUS 32
+#define VN_RESIZE_MAX_ROW_BYTES 24576
+int vn_resize_frames(const uint8_t* src_dev, int64_t n, int h, int w, int c, int oh, int ow,
+                     const double* taps_rows_host, int radius_rows, const double* taps_cols_host, int radius_cols,
+                     uint8_t* dst_dev, vn_stream_t stream);
+
 /* Per-env state tensors (device, [n_envs] int32 each): for checkpoint/resume and tests.
  * Order: scene, state, goal, obs_state, elapsed, episode(reset count), sched_pos.
  * Both are small stream-ordered kernels over the context's per-env records; vn_set_state
