@@ -136,6 +136,115 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict_
   }
 }
 
+// loss_grad_kernel plus the shortest-path expert term (DESIGN.md "Expert loss from the
+// navigation tables"): L_e = -w mean_i [M_i != 0] log q_i, q_i = sum_{a in M_i} p_a, M_i = the
+// bits of mask[i] below A (the env's optimal_mask of the state observed at sample i).
+//   d L_e / d logit_j = w inv_n (p_j - [j in M] exp(logp_j - log q))
+// log q comes from the log-probabilities, never from p_j / q: over the mask's actions as a
+// log-sum-exp, or, once the other actions hold less than half the mass, as log1p(-their mass),
+// so both a mask holding 1e-30 of the mass and one holding all of it keep their precision.
+// w = w0 (anneal_steps <= 0) or w0 max(0, 1 - *steps_dev / anneal_steps) in fp64, rounded once:
+// read from device memory, so a captured update anneals. pg scales the policy-gradient term
+// alone. With pg == 1 the A2C columns are loss_grad_kernel's own expression, and the expert
+// term is added last and only where w != 0 and M != 0: dout is then loss_grad_kernel's by bits.
+// stats: loss_grad_kernel's four (the policy term unscaled by pg); estats += block sums of
+// (-log q, [a in M], 1) over the samples with M != 0, estats[3] = w.
+__global__ __launch_bounds__(256) void loss_grad_expert_kernel(
+    const float* __restrict__ out, const int32_t* __restrict__ actions, const float* __restrict__ returns,
+    const uint8_t* __restrict__ mask, int n, int A, float vc, float ec, float pg, float inv_n, float w0,
+    const int64_t* __restrict__ steps_dev, int64_t anneal_steps, float* dout, float* stats, float* estats) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  float w = w0;
+  if (anneal_steps > 0) {
+    const double left = 1.0 - (double)*steps_dev / (double)anneal_steps;
+    w = (float)((double)w0 * fmax(0.0, left));
+  }
+  if (i == 0) estats[3] = w;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, e0 = 0.f, e1 = 0.f, e2 = 0.f;
+  if (i < n) {
+    float lg[7], p[7], lp[7], H;
+    for (int j = 0; j < A; ++j) lg[j] = out[(int64_t)i * OUT_LD_A2C + j];
+    softmax_stats_loss(lg, A, p, lp, H);
+    const int a = actions[i];
+    const float R = returns[i];
+    const float V = out[(int64_t)i * OUT_LD_A2C + A];
+    const float adv = R - V;
+    const int M = mask[i] & ((1 << A) - 1);
+    float g[7];
+    if (pg == 1.0f) {
+      for (int j = 0; j < A; ++j) {
+        const float ind = (j == a) ? 1.0f : 0.0f;
+        g[j] = (-adv * (ind - p[j]) + ec * p[j] * (lp[j] + H)) * inv_n;
+      }
+    } else {
+      for (int j = 0; j < A; ++j) {
+        const float ind = (j == a) ? 1.0f : 0.0f;
+        g[j] = (pg * (-adv * (ind - p[j])) + ec * p[j] * (lp[j] + H)) * inv_n;
+      }
+    }
+    if (M != 0) {
+      float mx = -INFINITY, rest = 0.0f;
+      for (int j = 0; j < A; ++j) {
+        if ((M >> j) & 1)
+          mx = fmaxf(mx, lp[j]);
+        else
+          rest += p[j];
+      }
+      float lq;
+      if (rest < 0.5f) {
+        lq = log1pf(-rest);
+      } else {
+        float se = 0.0f;
+        for (int j = 0; j < A; ++j)
+          if ((M >> j) & 1) se += expf(lp[j] - mx);
+        lq = mx + logf(se);
+      }
+      if (w != 0.0f) {
+        const float wn = w * inv_n;
+        for (int j = 0; j < A; ++j) {
+          const float r = ((M >> j) & 1) ? expf(lp[j] - lq) : 0.0f;
+          g[j] = g[j] + wn * (p[j] - r);
+        }
+      }
+      e0 = -lq;
+      e1 = ((M >> a) & 1) ? 1.0f : 0.0f;
+      e2 = 1.0f;
+    }
+    for (int j = 0; j < A; ++j) dout[(int64_t)i * OUT_LD_A2C + j] = g[j];
+    dout[(int64_t)i * OUT_LD_A2C + A] = vc * (-2.0f * adv) * inv_n;
+    for (int j = A + 1; j < OUT_LD_A2C; ++j) dout[(int64_t)i * OUT_LD_A2C + j] = 0.0f;
+    s0 = adv * adv;
+    s1 = -adv * lp[a];
+    s2 = H;
+    s3 = R;
+  }
+  __shared__ float red[4][7];
+  for (int off = 32; off > 0; off >>= 1) {
+    s0 += __shfl_down(s0, off);
+    s1 += __shfl_down(s1, off);
+    s2 += __shfl_down(s2, off);
+    s3 += __shfl_down(s3, off);
+    e0 += __shfl_down(e0, off);
+    e1 += __shfl_down(e1, off);
+    e2 += __shfl_down(e2, off);
+  }
+  const int wv = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[wv][0] = s0;
+    red[wv][1] = s1;
+    red[wv][2] = s2;
+    red[wv][3] = s3;
+    red[wv][4] = e0;
+    red[wv][5] = e1;
+    red[wv][6] = e2;
+  }
+  __syncthreads();
+  if (threadIdx.x < 7) {
+    const float v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    atomicAdd(threadIdx.x < 4 ? &stats[threadIdx.x] : &estats[threadIdx.x - 4], v);
+  }
+}
+
 constexpr int kNormBlocks = 512;
 
 __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, int64_t n, float scale,
@@ -650,6 +759,23 @@ int vn_a2c_loss_grad(const float* out, const int32_t* actions, const float* retu
   VN_HIP(hipMemsetAsync(stats4, 0, 4 * sizeof(float), st));
   hipLaunchKernelGGL(loss_grad_kernel, dim3((n + 255) / 256), dim3(256), 0, st, out, actions, returns, n,
                      num_actions, value_coef, entropy_coef, 1.0f / (float)n, dout, stats4);
+  VN_HIP(hipGetLastError());
+  return VN_OK;
+}
+
+int vn_a2c_loss_grad_expert(const float* out, const int32_t* actions, const float* returns,
+                            const uint8_t* expert_mask, int n, int num_actions, float value_coef, float entropy_coef,
+                            float pg_coef, float expert_weight, const int64_t* steps_dev, int64_t anneal_steps,
+                            float* dout, float* stats4, float* expert_stats4, vn_stream_t stream) {
+  if (!out || !actions || !returns || !expert_mask || !dout || !stats4 || !expert_stats4 || n <= 0 ||
+      num_actions < 1 || num_actions > 7 || (anneal_steps > 0 && !steps_dev))
+    return fail(VN_EINVAL, "vn_a2c_loss_grad_expert: bad args");
+  hipStream_t st = (hipStream_t)stream;
+  VN_HIP(hipMemsetAsync(stats4, 0, 4 * sizeof(float), st));
+  VN_HIP(hipMemsetAsync(expert_stats4, 0, 4 * sizeof(float), st));
+  hipLaunchKernelGGL(loss_grad_expert_kernel, dim3((n + 255) / 256), dim3(256), 0, st, out, actions, returns,
+                     expert_mask, n, num_actions, value_coef, entropy_coef, pg_coef, 1.0f / (float)n, expert_weight,
+                     steps_dev, anneal_steps, dout, stats4, expert_stats4);
   VN_HIP(hipGetLastError());
   return VN_OK;
 }

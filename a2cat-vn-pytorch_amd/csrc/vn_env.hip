@@ -1644,6 +1644,7 @@ int vn_set_nav_buffers(vn_ctx* c, int32_t* geo_dist, int32_t* optimal_action, ui
   c->nav->geo_dist = geo_dist;
   c->nav->opt_action = optimal_action;
   c->nav->opt_mask = optimal_mask;
+  c->nav->opt_mask_out = nullptr;
   c->nav->ep_success = ep_success;
   c->nav->ep_spl = ep_spl;
   c->nav->ep_start = ep_start_dist;
@@ -1651,6 +1652,13 @@ int vn_set_nav_buffers(vn_ctx* c, int32_t* geo_dist, int32_t* optimal_action, ui
   const int rc = nav_launch(c->nav, NAV_FORM_OUTPUTS, c->recs, nullptr, nullptr, nullptr, 0);
   if (rc != VN_OK) return rc;
   VN_HIP(hipDeviceSynchronize());
+  return VN_OK;
+}
+
+int vn_set_nav_mask_output(vn_ctx* c, uint8_t* optimal_mask) {
+  if (!c) return fail(VN_EINVAL, "vn_set_nav_mask_output: NULL ctx");
+  if (!c->nav) return fail(VN_ESTATE, "vn_set_nav_mask_output: navigation info is not enabled (vn_nav_enable)");
+  c->nav->opt_mask_out = optimal_mask;
   return VN_OK;
 }
 

@@ -49,6 +49,8 @@ struct NavState {
   uint8_t* ep_success = nullptr;
   float* ep_spl = nullptr;
   int32_t* ep_start = nullptr;
+  // vn_set_nav_mask_output: where the following launches write the mask instead of opt_mask
+  uint8_t* opt_mask_out = nullptr;
 };
 
 // Allocates everything and builds the tables from the device graph ([rows][4] int32); the

@@ -239,7 +239,7 @@ int nav_launch(NavState* s, int form, const void* recs, const uint8_t* done, con
   a.ep_len = ep_len;
   a.geo_dist = s->geo_dist;
   a.opt_action = s->opt_action;
-  a.opt_mask = s->opt_mask;
+  a.opt_mask = s->opt_mask_out ? s->opt_mask_out : s->opt_mask;
   a.ep_success = s->ep_success;
   a.ep_spl = s->ep_spl;
   a.ep_start = s->ep_start;

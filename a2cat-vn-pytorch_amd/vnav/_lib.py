@@ -144,6 +144,7 @@ SIGNATURES = {
     "vn_step_aux": (c_int, [c_void_p, c_void_p, P(ObsSet), c_void_p, c_void_p, c_void_p, c_void_p]),
     "vn_nav_enable": (c_int, [c_void_p, c_int]),
     "vn_set_nav_buffers": (c_int, [c_void_p] + [c_void_p] * 6),
+    "vn_set_nav_mask_output": (c_int, [c_void_p, c_void_p]),
     "vn_nav_table": (c_int, [c_void_p, c_int, P(c_void_p), P(c_int32)]),
     "vn_get_nav_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vn_set_nav_state": (c_int, [c_void_p, c_void_p, c_void_p]),
@@ -211,6 +212,9 @@ SIGNATURES.update({
                                       c_int, c_float, c_void_p, c_void_p]),
     "vn_a2c_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int,
                                         c_float, c_float, c_void_p, c_void_p,
+                                        c_void_p]),
+    "vn_a2c_loss_grad_expert": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float,
+                                        c_float, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),
     "vn_a2c_step_post": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -67,7 +67,8 @@ class A2CTrainer:
                  aux_weight=0.0, arch="goal", cuda_graph=False, aux_source="rollout", replay_size=8,
                  capture_collectives=False, allreduce_buckets=1, time_collectives=False, dedup_goals=None,
                  unreal=False, pc_weight=0.05, rp_weight=1.0, vr_weight=1.0, pc_gamma=0.9, unreal_envs=16,
-                 unreal_source="rollout", nav_metrics=False):
+                 unreal_source="rollout", nav_metrics=False, expert_weight=None, expert_anneal_steps=0,
+                 pg_coefficient=1.0):
         self.env = env
         self.lib = _lib.load()
         # check before every replayed UNREAL pass that the side stream's buffers and gradient
@@ -137,6 +138,28 @@ class A2CTrainer:
             if not env.nav_info:
                 env.set_nav_info(True)
             self.nav_stats = torch.zeros(4, dtype=torch.float32, **kw)
+        # expert_weight (None = off): the shortest-path expert term -w mean log sum_{a in M} pi(a)
+        # on the rollout's samples, M = the env's optimal_mask of the state each sample observed
+        # (DESIGN.md "Expert loss from the navigation tables"). expert_mask [T, E]: step t's nav
+        # launch writes slot t + 1 (the state it leaves the env in is step t + 1's observation),
+        # slot 0 is copied from the env's own buffer when a rollout begins. expert_stats =
+        # [sum of -log q, agreeing samples, labelled samples, the weight used]; expert_steps =
+        # the env-step count the update's learning rate is computed from.
+        self.expert = expert_weight is not None
+        self.pg_coefficient = float(pg_coefficient)
+        if not self.expert and self.pg_coefficient != 1.0:
+            raise ValueError("pg_coefficient != 1 needs the expert term (expert_weight): without it nothing would "
+                             "train the policy head")
+        if self.expert:
+            self.expert_weight = float(expert_weight)
+            self.expert_anneal_steps = int(expert_anneal_steps)
+            if not env.nav_info:
+                env.set_nav_info(True)
+            if "optimal_mask" not in env._info:
+                raise ValueError("expert_weight needs the env's optimal_mask buffer (set_nav_info was given None)")
+            self.expert_mask = torch.zeros((T, E), dtype=torch.uint8, **kw)
+            self.expert_stats = torch.zeros(4, dtype=torch.float32, **kw)
+            self.expert_steps = torch.zeros(1, dtype=torch.int64, **kw)
         # device schedule: [next sampling-counter base (updates * T), env-steps so far, this
         # update's counter base] and the learning rate of the update (vn_a2c_schedule)
         self.sched = torch.zeros(3, dtype=torch.int64, **kw)
@@ -739,6 +762,12 @@ class A2CTrainer:
         # into their slots by the env step before them) and, recurrent, step 0's mask and
         # [one_hot(a) | r] * m from the carried last action / reward / mask
         rec = self.recurrent
+        if self.expert:
+            # slot 0 = the mask of the state this rollout starts from (the last step of the one
+            # before, a reset or a restored checkpoint left it in the env's own buffer), and the
+            # step count the schedule below computes this update's learning rate from
+            self.expert_mask[0].copy_(info["optimal_mask"])
+            self.expert_steps.copy_(self.sched[1:2])
         _lib.check(lib.vn_a2c_rollout_begin(
             _lib.ptr(self.sched), _lib.ptr(self.lr_dev), ctypes.c_double(self.learning_rate),
             ctypes.c_double(self.max_time_steps), ctypes.c_int64(N * self.world), T, _lib.ptr(info["img_row"]),
@@ -756,6 +785,8 @@ class A2CTrainer:
                 env.set_row_outputs(self.rows_img[nxt], self.rows_goal[nxt])
             else:
                 env.set_row_outputs(None, None)
+            if self.expert:  # the mask of the state this step leaves: step t + 1's label
+                env.set_nav_mask_output(self.expert_mask[t + 1] if t + 1 < T else None)
             # one launch: the categorical draw from out[t] (Philox counter = updates * T + t from
             # the device schedule), the index-only env step, and the next step's recurrent
             # inputs, carries and episode statistics
@@ -799,10 +830,18 @@ class A2CTrainer:
                     self._ev_u1.record(self._side_u)
         _lib.check(lib.vn_a2c_returns(_lib.ptr(self.rewards), _lib.ptr(self.dones), _lib.ptr(self.boot_out), T, E, A,
                                       ctypes.c_float(self.gamma), _lib.ptr(self.returns), st), "vn_a2c_returns")
-        _lib.check(lib.vn_a2c_loss_grad(_lib.ptr(self.out), _lib.ptr(self.actions), _lib.ptr(self.returns), N, A,
-                                        ctypes.c_float(self.value_coefficient),
-                                        ctypes.c_float(self.entropy_coefficient), _lib.ptr(self.dout),
-                                        _lib.ptr(self.stats), st), "vn_a2c_loss_grad")
+        if self.expert:  # the same launch shape, with the expert term: the update gains no launch
+            _lib.check(lib.vn_a2c_loss_grad_expert(
+                _lib.ptr(self.out), _lib.ptr(self.actions), _lib.ptr(self.returns), _lib.ptr(self.expert_mask), N, A,
+                ctypes.c_float(self.value_coefficient), ctypes.c_float(self.entropy_coefficient),
+                ctypes.c_float(self.pg_coefficient), ctypes.c_float(self.expert_weight), _lib.ptr(self.expert_steps),
+                ctypes.c_int64(self.expert_anneal_steps), _lib.ptr(self.dout), _lib.ptr(self.stats),
+                _lib.ptr(self.expert_stats), st), "vn_a2c_loss_grad_expert")
+        else:
+            _lib.check(lib.vn_a2c_loss_grad(_lib.ptr(self.out), _lib.ptr(self.actions), _lib.ptr(self.returns), N, A,
+                                            ctypes.c_float(self.value_coefficient),
+                                            ctypes.c_float(self.entropy_coefficient), _lib.ptr(self.dout),
+                                            _lib.ptr(self.stats), st), "vn_a2c_loss_grad")
         dx4 = None
         unreal_dh = None
         if self._merged_replay:
@@ -988,6 +1027,9 @@ class A2CTrainer:
             m[9:] /= self.world
         if self.nav_metrics:  # the four nav sums ride behind, summed over ranks
             m = torch.cat([m, vdist.reduce_metrics_(self.nav_stats.clone(), 0, self.group)])
+        if self.expert:  # then the three expert sums, summed over ranks too, and the weight used
+            m = torch.cat([m, vdist.reduce_metrics_(self.expert_stats[:3].clone(), 0, self.group),
+                           self.expert_stats[3:]])
         return m
 
     def _graph_update(self):
@@ -1026,15 +1068,24 @@ class A2CTrainer:
         if self.unreal:
             unreal = {"pc_loss": vals[9], "rp_loss": vals[10], "vr_loss": vals[11]}
         nav = {}
+        k = 12 if self.unreal else 9
         if self.nav_metrics:
-            n_ep, n_ok, spl_sum, _ = vals[-4:]
+            n_ep, n_ok, spl_sum, _ = vals[k:k + 4]
+            k += 4
             nav = {"success_rate": n_ok / n_ep if n_ep else float("nan"),
                    "spl": spl_sum / n_ep if n_ep else float("nan")}
+        expert, expert_term = {}, 0.0
+        if self.expert:
+            nlq, agree, valid, w = vals[k:k + 4]
+            expert = {"expert_loss": nlq / valid if valid else float("nan"),
+                      "expert_agreement": agree / valid if valid else float("nan"), "expert_weight": w}
+            expert_term = w * nlq / (N * self.world)  # w * expert_loss * valid / N
         dt = time.perf_counter() - t0
         return {
             "step": self.total_steps, "updates": self.num_updates,
             "value_loss": vl, "action_loss": al, "entropy": ent,
-            "loss": self.value_coefficient * vl + al - self.entropy_coefficient * ent + (
+            "loss": self.value_coefficient * vl + self.pg_coefficient * al - self.entropy_coefficient * ent +
+            expert_term + (
                 self.pc_weight * unreal["pc_loss"] + self.rp_weight * unreal["rp_loss"] +
                 self.vr_weight * unreal["vr_loss"] if unreal else 0.0),
             "episodes": eps, "reward": rsum / eps if eps else float("nan"),
@@ -1043,6 +1094,7 @@ class A2CTrainer:
             **({"aux_loss": aux_loss} if self.aux_weight > 0 else {}),
             **unreal,
             **nav,
+            **expert,
         }
 
     def run(self, log_every=10, logger=print):
@@ -1058,10 +1110,13 @@ class A2CTrainer:
         (or ``max_rollouts`` rollouts). The recurrent state carries across rollouts as in
         training; the learning-rate step count is left as it was. Returns the episode count
         and the mean reward and length of the finished episodes; with ``nav_metrics`` also
-        their success rate, mean SPL and mean start distance (geodesic, in actions)."""
+        their success rate, mean SPL and mean start distance (geodesic, in actions); with the
+        expert term on also ``expert_agreement``, the share of the labelled samples whose
+        sampled action starts a shortest path."""
         saved_sched = self.sched.clone()  # sampling counter and step count: evaluation leaves both
         E, T = self.env.num_envs, self.num_steps
         tot = torch.zeros(7 if self.nav_metrics else 3, dtype=torch.float64)
+        agree = torch.zeros(2, dtype=torch.float64)  # agreeing, labelled samples
         for _ in range(int(max_rollouts)):
             self.rollout()
             if self.recurrent:  # (h, c) after the last step carry on, as update() does
@@ -1071,6 +1126,11 @@ class A2CTrainer:
                 st = torch.cat([st, self.nav_stats.to(torch.float64)])
             vdist.reduce_metrics_(st, 0, self.group)
             tot += st.cpu()
+            if self.expert:
+                M = self.expert_mask.view(-1).to(torch.int32) & ((1 << self.A) - 1)
+                hit = (M >> self.actions) & 1
+                ag = torch.stack([hit.sum(), (M != 0).sum()]).to(torch.float64)
+                agree += vdist.reduce_metrics_(ag, 0, self.group).cpu()
             if tot[0] >= episodes:
                 break
         self.sched.copy_(saved_sched)
@@ -1082,6 +1142,8 @@ class A2CTrainer:
             nan = float("nan")
             out.update(success_rate=n_ok / n_ep if n_ep else nan, spl=spl_sum / n_ep if n_ep else nan,
                        start_distance=start_sum / n_ep if n_ep else nan)
+        if self.expert:
+            out["expert_agreement"] = float(agree[0] / agree[1]) if agree[1] else float("nan")
         return out
 
     _RECURRENT_STATE = ("h0", "c0", "prev_action", "prev_reward", "prev_mask")
@@ -1145,6 +1207,8 @@ class A2CTrainer:
                 warnings.warn("checkpoint holds no navigation state (saved without nav_metrics): the running "
                               "episodes are measured from their current positions")
                 self.env.set_nav_info(True)
+        if self.expert:  # the env's own mask buffer = the restored states' masks (the next rollout's slot 0)
+            self.env.refresh_nav_outputs()
         self.num_updates = int(sd["num_updates"])
         self.total_steps = int(sd["total_steps"])
         if "sched" in sd:

@@ -237,6 +237,24 @@ class VectorEnv:
         self._need_nav()
         return {k: self._info[k] for k, _ in NAV_KEYS if k in self._info}
 
+    def set_nav_mask_output(self, mask):
+        """Where the next steps write ``optimal_mask``: a uint8 [E] device tensor (e.g. a
+        trainer's per-step slot, so no copy follows each step), or None for the buffer
+        set_nav_info() was given (vn_set_nav_mask_output: a pointer swap, no launch, no sync).
+        The other navigation outputs stay where they are. The caller keeps the tensor alive."""
+        self._need_nav()
+        self._check_out("optimal_mask", mask, torch.uint8, self.num_envs)
+        _lib.check(self.lib.vn_set_nav_mask_output(self._ctx, _lib.ptr(mask)), "vn_set_nav_mask_output")
+
+    def refresh_nav_outputs(self):
+        """Rewrite distance, mask and action of every env's current state into the env's
+        navigation buffers (vn_set_nav_buffers with the same buffers: synchronises). For use
+        after set_state() + set_nav_state(), which leave them at the states before."""
+        self._need_nav()
+        bufs = [self._info.get(k) for k, _ in NAV_KEYS]
+        torch.cuda.synchronize(self.device)
+        _lib.check(self.lib.vn_set_nav_buffers(self._ctx, *[_lib.ptr(t) for t in bufs]), "vn_set_nav_buffers")
+
     def _need_nav(self):
         if not self.nav_info:
             raise _lib.VnavError("navigation info is off: VectorEnv(..., nav_info=True)")

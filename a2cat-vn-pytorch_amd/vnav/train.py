@@ -114,6 +114,12 @@ class Experiment:
     vr_weight = 1.0
     # success rate and SPL of the finished episodes (A2CTrainer nav_metrics; test() turns it on)
     nav_metrics = False
+    # shortest-path expert term from the navigation tables (A2CTrainer expert_weight; None = off),
+    # its linear annealing horizon in env-steps (0 = constant) and the policy-gradient scale
+    # (0 = imitation only)
+    expert_weight = None
+    expert_anneal_steps = 0
+    pg_coefficient = 1.0
 
     def __init__(self, env_kwargs=None, model_kwargs=None, save_dir=None, seed=0, device=None, logger=print,
                  **overrides):
@@ -151,7 +157,9 @@ class Experiment:
                           vr_weight=self.vr_weight, unreal_source=self.unreal_source,
                           # world > 1: only on explicit opt-in (the captured RCCL path is unvalidated)
                           cuda_graph=self.cuda_graph and (self.world == 1 or self.capture_collectives),
-                          capture_collectives=self.capture_collectives, nav_metrics=self.nav_metrics)
+                          capture_collectives=self.capture_collectives, nav_metrics=self.nav_metrics,
+                          expert_weight=self.expert_weight, expert_anneal_steps=self.expert_anneal_steps,
+                          pg_coefficient=self.pg_coefficient)
 
     def _setup(self):
         if self.trainer is None:
@@ -314,6 +322,9 @@ class Experiment:
                            fps=int((tr.total_steps - s0) / max(now - t0, 1e-9)))
                 if "spl" in m:
                     row.update(success_rate=window["ok"] / window["episodes"], spl=window["spl"] / window["episodes"])
+                for k in ("expert_loss", "expert_agreement", "expert_weight"):  # the last update's
+                    if k in m:
+                        row[k] = m[k]
                 self._log(row)
                 window = dict(episodes=0.0, rsum=0.0, lsum=0.0, ok=0.0, spl=0.0)
                 t0, s0 = now, tr.total_steps
@@ -454,6 +465,12 @@ def main(argv=None):
     p.add_argument("--resume", action="store_true", help="continue from the checkpoint in --save-dir")
     p.add_argument("--nav-metrics", action="store_true",
                    help="log success_rate and spl of the finished episodes while training (--test always does)")
+    p.add_argument("--expert-weight", type=float, default=None, metavar="W",
+                   help="add the shortest-path expert loss -W mean log pi(optimal actions) from the navigation tables")
+    p.add_argument("--expert-anneal", type=int, default=None, metavar="STEPS",
+                   help="anneal the expert weight linearly to 0 over STEPS env-steps (default: constant)")
+    p.add_argument("--imitation", action="store_true",
+                   help="imitation only: policy-gradient coefficient 0 (--expert-weight defaults to 1.0)")
     a = p.parse_args(argv)
     vdist.init_distributed()
     env_kwargs = {}
@@ -473,6 +490,16 @@ def main(argv=None):
         over["cuda_graph"] = True
     if a.nav_metrics:
         over["nav_metrics"] = True
+    if a.imitation:
+        over["pg_coefficient"] = 0.0
+        if a.expert_weight is None:
+            a.expert_weight = 1.0
+    if a.expert_weight is not None:
+        over["expert_weight"] = a.expert_weight
+    if a.expert_anneal is not None:
+        if a.expert_weight is None:
+            p.error("--expert-anneal needs --expert-weight (or --imitation)")
+        over["expert_anneal_steps"] = a.expert_anneal
     exp = make_trainer(a.name, env_kwargs=env_kwargs, save_dir=a.save_dir, seed=a.seed, **over)
     if a.test:
         exp.test(episodes=a.episodes)

@@ -358,6 +358,13 @@ int vn_nav_enable(vn_ctx* ctx, int on);
  * buffers. VN_ESTATE before vn_nav_enable. Synchronises. */
 int vn_set_nav_buffers(vn_ctx* ctx, int32_t* geo_dist, int32_t* optimal_action, uint8_t* optimal_mask,
                        uint8_t* ep_success, float* ep_spl, int32_t* ep_start_dist);
+/* Redirects only the optimal_mask output of the following nav launches to another [n_envs]
+ * device buffer, e.g. a trainer's per-step slot, as vn_set_info_buffers does for the row
+ * outputs: a host-side pointer swap, no launch and no synchronisation (a launch captured in a
+ * graph keeps the pointer it was recorded with). NULL restores the buffer given to
+ * vn_set_nav_buffers, which also drops any redirection. The caller owns the buffer and keeps it
+ * alive while launches may write it. VN_ESTATE before vn_nav_enable. */
+int vn_set_nav_mask_output(vn_ctx* ctx, uint8_t* optimal_mask_E);
 /* The scene's [n][n] int16 table on the device, indexed [goal][state]. */
 int vn_nav_table(vn_ctx* ctx, int scene, const int16_t** geo_dev, int32_t* n);
 /* The part of the nav record a checkpoint needs, [2][n_envs] int32 on the device: start
@@ -637,6 +644,27 @@ int vn_a2c_returns(const float* rewards, const uint8_t* dones, const float* boot
 int vn_a2c_loss_grad(const float* out, const int32_t* actions, const float* returns, int n,
                      int num_actions, float value_coef, float entropy_coef, float* dout,
                      float* stats4, vn_stream_t stream);
+/* vn_a2c_loss_grad with the shortest-path expert term (DESIGN.md "Expert loss from the
+ * navigation tables"), one launch of the same shape. expert_mask [n] uint8: per sample the
+ * optimal_mask of the state it observed; M = its bits below num_actions, M == 0 = no label
+ * (the sample adds nothing). With p, logp, H, adv as vn_a2c_loss_grad computes them and
+ * q = sum_{a in M} p_a (log q formed from the log-probabilities, finite and accurate however
+ * little mass the mask holds):
+ *   L = vc mean(A^2) - pg mean(A logp_a) - ec mean(H) - w mean([M != 0] log q)
+ *   dout[i][j] = (pg (-adv (ind - p_j)) + ec p_j (logp_j + H)) / n + w / n (p_j - [j in M] exp(logp_j - log q))
+ * the value column and columns > num_actions as vn_a2c_loss_grad. w = expert_weight when
+ * anneal_steps <= 0, else expert_weight * max(0, 1 - *steps_dev / anneal_steps) in fp64 rounded
+ * once to fp32; steps_dev is read on the device by the launch, so a captured update anneals.
+ * stats4 = vn_a2c_loss_grad's (the policy term unscaled by pg). expert_stats4 = [sum of -log q
+ * over the samples with M != 0, how many of them sampled an action in M, their number, w].
+ * Both are zeroed by the call. With pg_coef == 1 and w == 0 or every M == 0, dout equals
+ * vn_a2c_loss_grad's bit for bit. VN_EINVAL, nothing written: a NULL buffer (steps_dev may be
+ * NULL when anneal_steps <= 0), n <= 0, num_actions outside 1..7. */
+int vn_a2c_loss_grad_expert(const float* out, const int32_t* actions, const float* returns,
+                            const uint8_t* expert_mask, int n, int num_actions, float value_coef,
+                            float entropy_coef, float pg_coef, float expert_weight, const int64_t* steps_dev,
+                            int64_t anneal_steps, float* dout, float* stats4, float* expert_stats4,
+                            vn_stream_t stream);
 /* Rollout bookkeeping after env step t (one launch): the next step's recurrent inputs —
  * last action one-hot and last reward times the episode mask m = 1 - done, and m itself
  * (UnrealEnvBaseWrapper's extra input, models/goal.py:63-64; mask rule of MaskedRNN,
