@@ -1161,11 +1161,12 @@ void nav_fill(vn_ctx* c, EnvArgs& a) {
   if (!a.done) a.done = c->nav->s_done;
   if (!a.info_trunc) a.info_trunc = c->nav->s_trunc;
   if (!a.info_len) a.info_len = c->nav->s_len;
+  if (c->nav->log.capacity > 0 && !a.info_ret) a.info_ret = c->nav->s_ret;
 }
 // After the step's env_kernel launch (rc = its result), on the same stream.
 int nav_after_step(vn_ctx* c, const EnvArgs& a, int rc, hipStream_t stream) {
   if (rc != VN_OK || !c->nav) return rc;
-  return nav_launch(c->nav, NAV_FORM_STEP, c->recs, a.done, a.info_trunc, a.info_len, stream);
+  return nav_launch(c->nav, NAV_FORM_STEP, c->recs, a.done, a.info_trunc, a.info_len, a.info_ret, stream);
 }
 
 // Whether a launch writing to (obs, goal) may skip rows that already hold their frame. The
@@ -1450,7 +1451,7 @@ int vn_reset(vn_ctx* c, const int32_t* env_mask_dev, vn_stream_t stream) {
   a.mask = env_mask_dev;
   const int rc = launch_env<MODE_RESET>(c, a, (hipStream_t)stream);
   if (rc != VN_OK || !c->nav) return rc;
-  return nav_launch(c->nav, NAV_FORM_RESET, c->recs, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  return nav_launch(c->nav, NAV_FORM_RESET, c->recs, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }
 
 int vn_observe(vn_ctx* c, uint8_t* obs_dev, uint8_t* goal_dev, int32_t* state_dev, vn_stream_t stream) {
@@ -1622,7 +1623,7 @@ int vn_nav_enable(vn_ctx* c, int on) {
   int rc = nav_create(&nav, c->n_envs, ns, c->graph);
   if (rc != VN_OK) return rc;
   // every env's record from its current state: a running episode is measured from here
-  rc = nav_launch(nav, NAV_FORM_ENABLE, c->recs, nullptr, nullptr, nullptr, 0);
+  rc = nav_launch(nav, NAV_FORM_ENABLE, c->recs, nullptr, nullptr, nullptr, nullptr, 0);
   if (rc == VN_OK) {
     const hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) rc = hip_fail(e, "vn_nav_enable: build");
@@ -1649,7 +1650,7 @@ int vn_set_nav_buffers(vn_ctx* c, int32_t* geo_dist, int32_t* optimal_action, ui
   c->nav->ep_spl = ep_spl;
   c->nav->ep_start = ep_start_dist;
   // the new buffers hold the current distance, mask and action at once
-  const int rc = nav_launch(c->nav, NAV_FORM_OUTPUTS, c->recs, nullptr, nullptr, nullptr, 0);
+  const int rc = nav_launch(c->nav, NAV_FORM_OUTPUTS, c->recs, nullptr, nullptr, nullptr, nullptr, 0);
   if (rc != VN_OK) return rc;
   VN_HIP(hipDeviceSynchronize());
   return VN_OK;
@@ -1691,6 +1692,22 @@ int vn_nav_episode_stats(vn_ctx* c, float* stats4, vn_stream_t stream) {
   if (!c->nav) return fail(VN_ESTATE, "vn_nav_episode_stats: navigation info is not enabled (vn_nav_enable)");
   DeviceGuard guard(c->device);
   return nav_episode_stats(c->nav, stats4, (hipStream_t)stream);
+}
+
+int vn_nav_sample_episodes(vn_ctx* c, int scene, int dist_lo, int dist_hi, int count, uint64_t seed, uint32_t salt,
+                           int32_t* start_goal_dev, int32_t* dist_dev, int64_t* total_host, vn_stream_t stream) {
+  if (!c) return fail(VN_EINVAL, "vn_nav_sample_episodes: NULL ctx");
+  if (!c->nav) return fail(VN_ESTATE, "vn_nav_sample_episodes: navigation info is not enabled (vn_nav_enable)");
+  DeviceGuard guard(c->device);
+  return nav_sample_episodes(c->nav, scene, dist_lo, dist_hi, count, seed, salt, start_goal_dev, dist_dev,
+                             total_host, (hipStream_t)stream);
+}
+
+int vn_nav_set_episode_log(vn_ctx* c, const vn_episode_log* log) {
+  if (!c) return fail(VN_EINVAL, "vn_nav_set_episode_log: NULL ctx");
+  if (!c->nav) return fail(VN_ESTATE, "vn_nav_set_episode_log: navigation info is not enabled (vn_nav_enable)");
+  DeviceGuard guard(c->device);
+  return nav_set_episode_log(c->nav, log);
 }
 
 int vn_set_info_buffers(vn_ctx* c, float* ep_return, int32_t* ep_length, int32_t* terminal_state,

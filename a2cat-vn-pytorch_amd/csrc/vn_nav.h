@@ -7,6 +7,8 @@
 
 #include <vector>
 
+#include "../../include/vnav.h"
+
 namespace vn {
 
 // The words of the per-env record (EnvRec, vn_env.hip) the nav kernels read: three 16-byte
@@ -51,6 +53,15 @@ struct NavState {
   int32_t* ep_start = nullptr;
   // vn_set_nav_mask_output: where the following launches write the mask instead of opt_mask
   uint8_t* opt_mask_out = nullptr;
+  // vn_nav_set_episode_log: the caller's buffers (capacity 0 = off) and the stand-in for the
+  // ep_return info buffer, used only while a log is set
+  vn_episode_log log = {};
+  float* s_ret = nullptr;
+  // vn_nav_sample_episodes' scratch: qualifying pairs per goal and their exclusive scan
+  // ([max_n + 1], the last element the total)
+  int max_n = 0;
+  int32_t* ep_cnt = nullptr;
+  int64_t* ep_off = nullptr;
 };
 
 // Allocates everything and builds the tables from the device graph ([rows][4] int32); the
@@ -58,9 +69,13 @@ struct NavState {
 int nav_create(NavState** out, int n_envs, const std::vector<NavScene>& scenes, const int32_t* graph_dev);
 void nav_destroy(NavState* s);
 // One thread per env, after the env kernel on `stream`. done / trunc / ep_len: this step's
-// (NAV_FORM_STEP only).
+// (NAV_FORM_STEP only); ep_ret: the step's ep_return output, read only while a log is set.
 int nav_launch(NavState* s, int form, const void* recs, const uint8_t* done, const uint8_t* trunc,
-               const int32_t* ep_len, hipStream_t stream);
+               const int32_t* ep_len, const float* ep_ret, hipStream_t stream);
+// vn_nav_set_episode_log / vn_nav_sample_episodes on a live nav state (arguments checked here).
+int nav_set_episode_log(NavState* s, const vn_episode_log* log);
+int nav_sample_episodes(NavState* s, int scene, int dist_lo, int dist_hi, int count, uint64_t seed, uint32_t salt,
+                        int32_t* start_goal, int32_t* dist, int64_t* total_host, hipStream_t stream);
 int nav_episode_stats(NavState* s, float* stats4, hipStream_t stream);
 
 }  // namespace vn

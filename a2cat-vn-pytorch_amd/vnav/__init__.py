@@ -8,6 +8,7 @@ from .scenes import (Scene, grid_tables, load_graph_pickle, load_h5, load_npz, m
                      oriented_tables, resize_frames, resize_scene, resize_taps, scene_from_arrays,
                      synthetic_scene)
 from .envs import CachedThorEnv, VectorEnv, make, to_float_chw  # noqa: F401
+from .episodes import EpisodeSet  # noqa: F401
 from .policy import BigHousePolicy, GoalNavPolicy, PolicyNet  # noqa: F401
 from .a2c import A2CTrainer  # noqa: F401
 from ._lib import VnavError  # noqa: F401

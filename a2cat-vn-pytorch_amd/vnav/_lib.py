@@ -106,6 +106,20 @@ class ReplaySeg(ctypes.Structure):
     ]
 
 
+class EpisodeLog(ctypes.Structure):
+    """vn_episode_log (include/vnav.h)."""
+    _fields_ = [
+        ("capacity", c_int32),
+        ("want", c_void_p),
+        ("count", c_void_p),
+        ("success", c_void_p),
+        ("length", c_void_p),
+        ("start_dist", c_void_p),
+        ("spl", c_void_p),
+        ("ep_return", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes). Every symbol here is declared in include/vnav.h.
 SIGNATURES = {
     "vn_version": (ctypes.c_char_p, []),
@@ -149,6 +163,9 @@ SIGNATURES = {
     "vn_get_nav_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vn_set_nav_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vn_nav_episode_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vn_nav_sample_episodes": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_uint32, c_void_p, c_void_p,
+                                       P(c_int64), c_void_p]),
+    "vn_nav_set_episode_log": (c_int, [c_void_p, P(EpisodeLog)]),
 }
 
 SIGNATURES.update({

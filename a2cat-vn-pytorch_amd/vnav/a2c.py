@@ -1148,6 +1148,173 @@ class A2CTrainer:
 
     _RECURRENT_STATE = ("h0", "c0", "prev_action", "prev_reward", "prev_mask")
 
+    # -- fixed-episode evaluation (DESIGN.md "Fixed-episode evaluation") ----------------------
+    def _rollout_greedy(self):
+        """rollout() with the argmax action instead of the sampled one, composed of existing
+        entry points: the forward, explicit heads, vn_policy_greedy, an index-only vn_step and
+        vn_a2c_step_post. No statistics are kept: the evaluation reads the episode log."""
+        env, lib, P = self.env, self.lib, _lib.ptr
+        E, T, A = env.num_envs, self.num_steps, self.A
+        info, rec = env._info, self.recurrent
+        _lib.check(lib.vn_a2c_rollout_begin(
+            P(self.sched), P(self.lr_dev), ctypes.c_double(self.learning_rate),
+            ctypes.c_double(self.max_time_steps), ctypes.c_int64(T * E * self.world), T, P(info["img_row"]),
+            P(info["goal_row"]), P(self.rows_img), P(self.rows_goal), E,
+            P(self.prev_action) if rec else None, P(self.prev_reward) if rec else None,
+            P(self.prev_mask) if rec else None, A, P(self.masks) if rec else None,
+            P(self.lra) if rec else None, self._stream()), "vn_a2c_rollout_begin")
+        scratch = torch.zeros(3, dtype=torch.float32, device=self.device)
+        for t in range(T):
+            sl = slice(t * E, (t + 1) * E)
+            self._policy_step(t, self._frames(self.rows_img[sl], self.rows_goal[sl]))
+            if self._fused_heads:  # the sampled step computes the heads itself
+                self.net.heads(self.params, self.h_all[sl], E, self.out[sl])
+            nxt = slice((t + 1) * E, (t + 2) * E)
+            if t + 1 < T:
+                env.set_row_outputs(self.rows_img[nxt], self.rows_goal[nxt])
+            else:
+                env.set_row_outputs(None, None)
+            _lib.check(lib.vn_policy_greedy(P(self.out[sl]), E, A, P(self.actions[sl]), self._stream()),
+                       "vn_policy_greedy")
+            env.step(self.actions[sl], out=dict(reward=self.rewards[t], done=self.dones[t], state=self.states),
+                     gather=False)
+            _lib.check(lib.vn_a2c_step_post(
+                P(self.actions[sl]), P(self.rewards[t]), P(self.dones[t]), P(info["ep_return"]), P(info["ep_length"]),
+                E, A, P(self.prev_action) if rec else None, P(self.prev_reward) if rec else None,
+                P(self.prev_mask) if rec else None,
+                P(self.lra[t + 1] if t + 1 < T else self.boot_lra) if rec else None,
+                P(self.masks[t + 1] if t + 1 < T else self.boot_mask) if rec else None, P(scratch), self._stream()),
+                "vn_a2c_step_post")
+
+    def evaluate_episodes(self, episode_set, policy="sample", max_episode_steps=None, seed=0):
+        """Run every episode of ``episode_set`` (vnav.EpisodeSet) exactly once with the current
+        policy and leave the trainer and its envs as they were. ``policy``: "sample" (the
+        rollout's categorical draw) or "greedy" (argmax). ``max_episode_steps``: the time limit
+        during the evaluation (default: the env's own; every episode must end, so there must be
+        one). ``seed`` fixes the sampling counters: the same set, parameters and seed give the
+        same results. Needs ``nav_metrics=True``.
+        The episodes are placed statically (episodes.assign_episodes): scenes get envs in
+        proportion to their episode counts, a scene's j-th episode runs on its (j mod m)-th env
+        as that env's (j div m)-th episode, by an exact-replay schedule; the results come from the
+        per-episode log alone, so episodes an env runs after its list are never counted. At world
+        > 1 rank r runs the episodes j = r (mod world); the sums are reduced over ranks, the
+        per-episode arrays are this rank's (``index`` holds their positions in the set).
+        Returns a dict: ``episodes``, ``success_rate``, ``spl``, ``episode_length``, ``reward``,
+        ``start_distance`` over all episodes, ``buckets`` (a list of the same per distance
+        bucket, with ``bucket`` = (lo, hi)), and ``per_episode`` (arrays ``index``, ``success``,
+        ``length``, ``spl``, ``start_distance``, ``reward``)."""
+        from . import episodes as vep
+        env = self.env
+        if not self.nav_metrics:
+            raise ValueError("evaluate_episodes needs A2CTrainer(nav_metrics=True)")
+        if policy not in ("sample", "greedy"):
+            raise ValueError('policy must be "sample" or "greedy", got %r' % (policy,))
+        limit = int(env.max_episode_steps if max_episode_steps is None else max_episode_steps)
+        if limit <= 0:
+            raise ValueError("evaluate_episodes needs a time limit > 0: every episode must end")
+        if len(episode_set) == 0:
+            raise ValueError("the episode set is empty")
+        episode_set.validate(env)
+        index = vep.world_slice(len(episode_set), self.rank, self.world)
+        per = {k: np.zeros(0, dtype=dt) for k, dt in (("success", bool), ("length", np.int32), ("spl", np.float32),
+                                                      ("start_distance", np.int32), ("reward", np.float32))}
+        if len(index):
+            per = self._run_episodes(episode_set.subset(index), policy, limit, int(seed))
+        per["index"] = index
+        # sums per bucket (the last row: all episodes), reduced over ranks in fp64
+        nb = len(episode_set.buckets)
+        bucket = episode_set.bucket[index]
+        sums = np.zeros((nb + 1, 6), dtype=np.float64)
+        for b in range(nb + 1):
+            sel = np.ones(len(index), dtype=bool) if b == nb else bucket == b
+            sums[b] = [sel.sum(), per["success"][sel].sum(), per["spl"][sel].astype(np.float64).sum(),
+                       per["length"][sel].sum(), per["reward"][sel].astype(np.float64).sum(),
+                       per["start_distance"][sel].sum()]
+        if self.world > 1:
+            sums = vdist.reduce_metrics_(torch.as_tensor(sums, device=self.device), 0, self.group).cpu().numpy()
+
+        def means(row):
+            n = row[0]
+            d = n if n else float("nan")
+            return {"episodes": int(n), "success_rate": row[1] / d, "spl": row[2] / d, "episode_length": row[3] / d,
+                    "reward": row[4] / d, "start_distance": row[5] / d}
+        out = means(sums[nb])
+        out["buckets"] = [dict(means(sums[b]), bucket=episode_set.buckets[b]) for b in range(nb)]
+        out["per_episode"] = per
+        return out
+
+    def _run_episodes(self, eps, policy, limit, seed):
+        """evaluate_episodes on this rank's episodes: the per-episode arrays in their order."""
+        from . import episodes as vep
+        env = self.env
+        E, T = env.num_envs, self.num_steps
+        env_scenes, ep_env, ep_slot, want, slots = vep.assign_episodes(eps.scene, E, len(env.scenes))
+        # [E, slots, 2] (start, goal): an env's unused slots repeat a valid pair of its scene
+        first = {int(k): int(np.nonzero(eps.scene == k)[0][0]) for k in np.unique(eps.scene)}
+        pad = np.array([first[int(k)] for k in env_scenes])
+        sched = np.stack([eps.start[pad], eps.goal[pad]], axis=1)[:, None, :].repeat(slots, axis=1).astype(np.int32)
+        sched[ep_env, ep_slot, 0], sched[ep_env, ep_slot, 1] = eps.start, eps.goal
+        # what the evaluation changes, saved
+        torch.cuda.synchronize(self.device)
+        saved = dict(schedule=env._schedule, env_scenes=env.env_scenes.copy(), limit=env.max_episode_steps,
+                     state=env.get_state().clone(), returns=env.get_episode_returns().clone(),
+                     nav=env.get_nav_state().clone(), sched=self.sched.clone(), lr=self.lr_dev.clone(),
+                     stats_env=self.stats_env.clone(), episode_stats=self.episode_stats.clone(),
+                     nav_stats=self.nav_stats.clone())
+        if self.recurrent:
+            saved["carry"] = {k: getattr(self, k).clone() for k in self._RECURRENT_STATE}
+        try:
+            env.set_env_scenes(env_scenes)
+            env.set_max_episode_steps(limit)
+            env.set_schedule(sched)
+            log = env.set_episode_log(slots, want)
+            _lib.check(self.lib.vn_reset(env._ctx, None, env._stream()), "vn_reset")
+            env.observe(gather=False)
+            # the sampling counter base from the seed; carries and last action / reward / mask zero
+            self.sched.copy_(torch.tensor([(seed & 0xFFFFFFFF) << 20, int(saved["sched"][1]), 0], dtype=torch.int64))
+            if self.recurrent:
+                for k in self._RECURRENT_STATE:
+                    getattr(self, k).zero_()
+            bound = slots * limit + T
+            steps = 0
+            while True:
+                if policy == "greedy":
+                    self._rollout_greedy()
+                else:
+                    self.rollout()
+                if self.recurrent:
+                    self._carry_states()
+                steps += T
+                if int(log.remaining()) == 0:  # one poll per rollout
+                    break
+                if steps >= bound:
+                    raise RuntimeError("evaluate_episodes: %d episodes unfinished after %d steps (bound %d)"
+                                       % (int(log.remaining()), steps, bound))
+            g = (torch.as_tensor(ep_slot, device=self.device), torch.as_tensor(ep_env, device=self.device))
+            per = {"success": log.success[g].cpu().numpy().astype(bool), "length": log.length[g].cpu().numpy(),
+                   "spl": log.spl[g].cpu().numpy(), "start_distance": log.start_distance[g].cpu().numpy(),
+                   "reward": log.ep_return[g].cpu().numpy()}
+        finally:
+            # everything back: configuration first, then the per-env state it would reset
+            env.set_episode_log(None)
+            env.set_schedule(saved["schedule"])
+            env.set_env_scenes(saved["env_scenes"])
+            env.set_max_episode_steps(saved["limit"])
+            env.set_state(saved["state"])
+            env.set_episode_returns(saved["returns"])
+            env.set_nav_state(saved["nav"])
+            env.nav_episode_stats()  # the per-env accumulators of the surplus episodes: dropped
+            env.refresh_nav_outputs()
+            env.observe(gather=False)
+            for k in ("sched", "stats_env", "episode_stats", "nav_stats"):
+                getattr(self, k).copy_(saved[k])
+            self.lr_dev.copy_(saved["lr"])
+            if self.recurrent:
+                for k, v in saved["carry"].items():
+                    getattr(self, k).copy_(v)
+            torch.cuda.synchronize(self.device)
+        return per
+
     def state_dict(self):
         sd = {"params": self.params.detach().cpu(), "square_avg": self.square_avg.cpu(),
               "env_state": self.env.get_state().cpu(), "env_ep_return": self.env.get_episode_returns().cpu(),

@@ -44,6 +44,28 @@ def to_float_chw(frames):
     return frames.permute(*range(frames.dim() - 3), -1, -3, -2).to(torch.float32) / 255.0
 
 
+class EpisodeLog:
+    """The per-episode log's device tensors (VectorEnv.set_episode_log): slot k of env e is
+    element [k, e]; only slots k < min(count[e], want[e]) hold an episode."""
+    FIELDS = (("success", torch.uint8), ("length", torch.int32), ("start_distance", torch.int32),
+              ("spl", torch.float32), ("ep_return", torch.float32))
+
+    def __init__(self, capacity, want, num_envs, device):
+        self.capacity = capacity
+        self.want = want
+        self.count = torch.zeros(num_envs, dtype=torch.int32, device=device)
+        for k, dt in self.FIELDS:
+            setattr(self, k, torch.zeros((capacity, num_envs), dtype=dt, device=device))
+
+    def _struct(self):
+        return _lib.EpisodeLog(self.capacity, *[t.data_ptr() for t in (
+            self.want, self.count, self.success, self.length, self.start_distance, self.spl, self.ep_return)])
+
+    def remaining(self):
+        """Episodes still to record, summed over envs (a device scalar)."""
+        return (self.want - self.count).clamp(min=0).sum()
+
+
 class VectorEnv:
     num_actions = 4  # THORDiscreteCachedEnv.get_action_size (cached.py:66-68)
 
@@ -122,6 +144,9 @@ class VectorEnv:
                                           self.device.index, ctypes.byref(handle)), "vn_create")
         self._ctx = handle
         self.nav_info = False
+        self.episode_log = None
+        # the env -> scene assignment (vn_set_env_scenes; the native default)
+        self.env_scenes = np.arange(self.num_envs, dtype=np.int32) % len(self.scenes)
         # bumped by every call that replaces the kernels' per-ctx configuration (tables,
         # schedules, limits): a captured hipGraph holds the old launch arguments and must be
         # recaptured (A2CTrainer checks it before each replay)
@@ -221,6 +246,7 @@ class VectorEnv:
         for k, _ in NAV_KEYS:
             self._info.pop(k, None)
         self.nav_info = False
+        self.episode_log = None  # the log lives in the nav state
         _lib.check(self.lib.vn_nav_enable(self._ctx, 1 if on else 0), "vn_nav_enable")
         if not on:
             return
@@ -302,8 +328,55 @@ class VectorEnv:
         # the copy is stream-ordered: keep the source alive until it has run
         buf.record_stream(torch.cuda.current_stream(self.device))
 
+    # -- fixed-episode evaluation (DESIGN.md "Fixed-episode evaluation") -------
+    def sample_episodes(self, scene_index, count, min_distance=1, max_distance=None, seed=0, salt=0):
+        """Draw ``count`` (start, goal) pairs of a scene, with replacement, uniformly among the
+        pairs whose action-graph geodesic distance lies in [min_distance, max_distance]
+        (vn_nav_sample_episodes: on the device, exact, reproducible from seed and salt).
+        Returns (pairs int32 [count, 2] = (start, goal), distance int32 [count], total) with
+        total the number of qualifying pairs; total == 0 leaves both tensors at -1."""
+        self._need_nav()
+        count = int(count)
+        hi = 32767 if max_distance is None else int(max_distance)
+        pairs = torch.full((max(count, 0), 2), -1, dtype=torch.int32, device=self.device)
+        dist = torch.full((max(count, 0),), -1, dtype=torch.int32, device=self.device)
+        total = ctypes.c_int64(0)
+        _lib.check(self.lib.vn_nav_sample_episodes(self._ctx, int(scene_index), int(min_distance), hi, count,
+                                                   ctypes.c_uint64(int(seed) & (2**64 - 1)),
+                                                   ctypes.c_uint32(int(salt) & 0xFFFFFFFF), _lib.ptr(pairs),
+                                                   _lib.ptr(dist), ctypes.byref(total), self._stream()),
+                   "vn_nav_sample_episodes")
+        return pairs, dist, total.value
+
+    def set_episode_log(self, capacity, want=None):
+        """Record every env's first ``want[e]`` (<= capacity) finished episodes, one slot each
+        (vn_nav_set_episode_log). Returns the EpisodeLog holding the device tensors: ``count``
+        int32 [E] (episodes finished since the call) and, [capacity, E] each, ``success``,
+        ``length``, ``start_distance``, ``spl``, ``ep_return``. ``set_episode_log(None)``
+        switches the log off. Replaces launch arguments: a captured graph must be recaptured."""
+        self._need_nav()
+        self.config_generation += 1
+        if capacity is None:
+            _lib.check(self.lib.vn_nav_set_episode_log(self._ctx, None), "vn_nav_set_episode_log")
+            self.episode_log = None
+            return None
+        capacity = int(capacity)
+        if capacity <= 0:
+            raise ValueError("episode log: capacity must be positive")
+        want = torch.as_tensor(want).to(device=self.device, dtype=torch.int32).contiguous()
+        if want.shape != (self.num_envs,):
+            raise ValueError("episode log: want must have one entry per env")
+        if int(want.min()) < 0 or int(want.max()) > capacity:
+            raise ValueError("episode log: want must lie in 0..capacity")
+        log = EpisodeLog(capacity, want, self.num_envs, self.device)
+        torch.cuda.synchronize(self.device)  # the buffers' fill precedes the call's own write
+        _lib.check(self.lib.vn_nav_set_episode_log(self._ctx, ctypes.byref(log._struct())), "vn_nav_set_episode_log")
+        self.episode_log = log
+        return log
+
     # -- configuration -------------------------------------------------------
     def set_max_episode_steps(self, n):
+        self.max_episode_steps = int(n or 0)
         self.config_generation += 1
         _lib.check(self.lib.vn_set_max_episode_steps(self._ctx, int(n or 0)), "vn_set_max_episode_steps")
 
@@ -321,6 +394,7 @@ class VectorEnv:
         self.config_generation += 1
         _lib.check(self.lib.vn_set_env_scenes(self._ctx, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
                    "vn_set_env_scenes")
+        self.env_scenes = arr.copy()
 
     def set_schedule(self, schedule):
         """Exact-replay test mode: schedule [E, L, 2] int32 (start, goal) per reset."""

@@ -5,6 +5,8 @@ driven by experiments/thor_cached_auxiliary.py:26-84).
 
     python -m vnav.train thor-cached-auxiliary [--scene thor-cached-212-174.pkl] [--save-dir D]
     python -m vnav.train thor-cached-auxiliary --test [--episodes 100]      # test-train.py
+    python -m vnav.train NAME --test --eval-episodes 100 [--eval-buckets 1-3,4-8,9-] [--greedy]
+        [--eval-set FILE] [--save-eval-set FILE]      # every episode of a fixed, distance-stratified set once
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m vnav.train cached-thor --envs 4096
     python -m vnav.train cached-thor --scene dump-300x400.npz --image-size 84 84   # resized on the device
 
@@ -346,6 +348,13 @@ class Experiment:
         a single-process file also restores its env state. Raises FileNotFoundError when
         there is no checkpoint (evaluating untrained weights would be silent nonsense). The
         result also carries the episodes' success rate, mean SPL and mean start distance."""
+        self._load_for_test(checkpoint)
+        n = episodes or self.validation_episodes or 100
+        res = self.trainer.evaluate(episodes=n)
+        self._log(dict(step=self.trainer.total_steps, **res))
+        return res
+
+    def _load_for_test(self, checkpoint=None):
         path = checkpoint or self.checkpoint_path
         if not os.path.exists(path):
             raise FileNotFoundError("no checkpoint to test: %s (train first, or pass checkpoint=)" % path)
@@ -357,9 +366,31 @@ class Experiment:
             tr.load_params_state_dict(sd)
         else:
             tr.load_state_dict(sd)
-        n = episodes or self.validation_episodes or 100
-        res = self.trainer.evaluate(episodes=n)
-        self._log(dict(step=self.trainer.total_steps, **res))
+        return tr
+
+    def test_episodes(self, per_bucket=None, buckets=None, greedy=False, eval_set=None, save_eval_set=None,
+                      max_episode_steps=None, checkpoint=None):
+        """The saved policy on a fixed episode set (A2CTrainer.evaluate_episodes): ``eval_set``
+        (an .npz written by ``save_eval_set``) or, sampled from the scenes' geodesic tables with
+        this experiment's seed, ``per_bucket`` episodes per scene and distance bucket. Logs one
+        table row per bucket and one over all episodes; returns evaluate_episodes' result."""
+        from .episodes import DEFAULT_BUCKETS, EpisodeSet
+        tr = self._load_for_test(checkpoint)
+        if eval_set:
+            eps = EpisodeSet.load(eval_set)
+        else:
+            eps = EpisodeSet.sample(tr.env, int(per_bucket or self.validation_episodes or 100),
+                                    buckets=buckets or DEFAULT_BUCKETS, seed=self.seed)
+        if save_eval_set and self.rank == 0:
+            eps.save(save_eval_set)
+        res = tr.evaluate_episodes(eps, policy="greedy" if greedy else "sample", max_episode_steps=max_episode_steps,
+                                   seed=self.seed)
+        keys = ("episodes", "success_rate", "spl", "episode_length", "reward", "start_distance")
+        for row in res["buckets"]:
+            lo, hi = row["bucket"]
+            self._log(dict(step=tr.total_steps, distance="%d-%s" % (lo, "" if hi is None else hi),
+                           **{k: row[k] for k in keys}))
+        self._log(dict(step=tr.total_steps, distance="all", **{k: res[k] for k in keys}))
         return res
 
 
@@ -460,6 +491,15 @@ def main(argv=None):
     p.add_argument("--max-time-steps", type=float, default=None)
     p.add_argument("--save-dir", default=None)
     p.add_argument("--episodes", type=int, default=None, help="--test: episodes to run")
+    p.add_argument("--eval-episodes", type=int, default=None, metavar="N",
+                   help="--test on a fixed episode set: N episodes per scene and distance bucket, each run once")
+    p.add_argument("--eval-buckets", default=None, metavar="LO-HI,...",
+                   help="geodesic distance buckets of --eval-episodes (default 1-3,4-8,9-)")
+    p.add_argument("--greedy", action="store_true", help="fixed-set --test: argmax actions instead of sampled ones")
+    p.add_argument("--eval-set", default=None, metavar="FILE", help="fixed-set --test: load the episode set")
+    p.add_argument("--save-eval-set", default=None, metavar="FILE", help="fixed-set --test: save the episode set")
+    p.add_argument("--eval-max-steps", type=int, default=None, metavar="N",
+                   help="fixed-set --test: the time limit of an evaluation episode (default: the env's)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--cuda-graph", action="store_true", help="replay each update as a captured hipGraph (1 GPU)")
     p.add_argument("--resume", action="store_true", help="continue from the checkpoint in --save-dir")
@@ -501,7 +541,17 @@ def main(argv=None):
             p.error("--expert-anneal needs --expert-weight (or --imitation)")
         over["expert_anneal_steps"] = a.expert_anneal
     exp = make_trainer(a.name, env_kwargs=env_kwargs, save_dir=a.save_dir, seed=a.seed, **over)
-    if a.test:
+    fixed = a.eval_episodes is not None or a.eval_set is not None
+    if not fixed and (a.eval_buckets or a.greedy or a.save_eval_set or a.eval_max_steps is not None):
+        p.error("--eval-buckets / --greedy / --save-eval-set / --eval-max-steps need --eval-episodes or --eval-set")
+    if fixed and not a.test:
+        p.error("--eval-episodes / --eval-set need --test")
+    if a.test and fixed:
+        from .episodes import parse_buckets
+        exp.test_episodes(per_bucket=a.eval_episodes, buckets=parse_buckets(a.eval_buckets) if a.eval_buckets else None,
+                          greedy=a.greedy, eval_set=a.eval_set, save_eval_set=a.save_eval_set,
+                          max_episode_steps=a.eval_max_steps)
+    elif a.test:
         exp.test(episodes=a.episodes)
     else:
         exp.run(resume=a.resume)

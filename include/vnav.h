@@ -376,6 +376,43 @@ int vn_set_nav_state(vn_ctx* ctx, const int32_t* src_dev_2xE, vn_stream_t stream
  * accumulators are then zeroed. Same inputs, same bits. No host argument: capturable. */
 int vn_nav_episode_stats(vn_ctx* ctx, float* stats4_dev, vn_stream_t stream);
 
+/* Fixed-episode evaluation (DESIGN.md "Fixed-episode evaluation").
+ * Draws `count` (start, goal) pairs of `scene`, with replacement, uniformly from
+ * Q = {(g, s) : dist_lo <= geo[g][s] <= dist_hi}, Q ordered by g, then by s. Exact, so a host
+ * restatement reproduces it bit for bit: draw j takes r = Philox4x32-10((j, 0, salt, 5), key =
+ * seed), u = r.x * 2^32 + r.y, idx = (u * total) >> 64 with total = |Q| (<= 2^28), and is the
+ * idx-th pair of Q. dist_lo >= 1, so the goal itself and unreachable pairs (-1) never qualify;
+ * dist_hi is clamped to 32767. start_goal_dev [count][2] = (start, goal); dist_dev [count] =
+ * geo[g][s] of each pair, may be NULL; *total_host = |Q|. total == 0 returns VN_OK and writes no
+ * pair. Off the step path: three small launches on `stream`, and the call synchronises with it.
+ * Its scratch belongs to the nav state. VN_ESTATE before vn_nav_enable. VN_EINVAL, with nothing
+ * written: scene out of range, dist_lo < 1, dist_hi < dist_lo, count <= 0, NULL start_goal_dev
+ * or total_host. */
+int vn_nav_sample_episodes(vn_ctx* ctx, int scene, int dist_lo, int dist_hi, int count, uint64_t seed,
+                           uint32_t salt, int32_t* start_goal_dev, int32_t* dist_dev, int64_t* total_host,
+                           vn_stream_t stream);
+/* Per-episode log of the nav step. The buffers are the caller's, on the device; nothing is
+ * allocated per step. While a log is set, the nav launch behind every vn_step* does, for an env
+ * with done: k = count[e]; if k < want[e] it writes slot k (index k * n_envs + e) with exactly
+ * the values the step's own ep_success / ep_spl / ep_start_dist outputs carry, the finished
+ * episode's length minus the nav length offset and its return; then count[e] = k + 1. Slots at
+ * or beyond want[e] are never written. The return is read from the ep_return info buffer
+ * (vn_set_info_buffers), or from a stand-in of the nav state where the caller set none.
+ * The call zeroes count, replaces launch arguments like the vn_set_* calls (it synchronises; a
+ * captured graph holds the arguments it was recorded with), and log = NULL switches the log
+ * off. VN_ESTATE before vn_nav_enable; VN_EINVAL for capacity <= 0 or any NULL buffer. */
+typedef struct vn_episode_log {
+  int32_t capacity;    /* slots per env */
+  const int32_t* want; /* [n_envs] episodes to record for env e, 0..capacity */
+  int32_t* count;      /* [n_envs] finished so far; zeroed by the call */
+  uint8_t* success;    /* [capacity][n_envs], slot-major: adjacent envs write adjacent bytes */
+  int32_t* length;     /* finished episode's length minus the nav length offset */
+  int32_t* start_dist;
+  float* spl;
+  float* ep_return;
+} vn_episode_log;
+int vn_nav_set_episode_log(vn_ctx* ctx, const vn_episode_log* log);
+
 /* Scene-cache arena: all scenes' frames back to back, row = frame. */
 int vn_frame_arena(vn_ctx* ctx, const uint8_t** arena_dev, int64_t* frame_bytes,
                    int64_t* n_rows);
