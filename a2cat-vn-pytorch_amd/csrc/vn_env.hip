@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -35,6 +36,7 @@
 #include <vector>
 
 #include "vn_common.h"
+#include "vn_curriculum.h"
 #include "vn_nav.h"
 #include "vn_unit_float.h"
 
@@ -1104,6 +1106,11 @@ struct vn_ctx {
   AuxRec* arecs = nullptr;
   // vn_nav_enable: the geodesic tables, the per-env nav record and its outputs (vn_nav.hip)
   NavState* nav = nullptr;
+  // vn_nav_curriculum: the geodesic start tables, counters and levels (vn_curriculum.hip). While
+  // it is set the reset path reads its tables, and scenes_spd keeps the scene table as it was
+  // (cnt_off, maxd, cur_oi, cur_mode of the spd curriculum) for switching it off again
+  CurState* cur = nullptr;
+  std::vector<SceneDev> scenes_spd;
 };
 
 namespace {
@@ -1131,9 +1138,9 @@ EnvArgs make_args(vn_ctx* c) {
   a.env_scene = c->env_scene;
   a.tasks = c->tasks;
   a.sched = c->sched;
-  a.cur_order = c->cur_order;
-  a.cur_count = c->cur_count;
-  a.cur_mode = c->cur_mode;
+  a.cur_order = c->cur ? c->cur->order : c->cur_order;
+  a.cur_count = c->cur ? c->cur->count : c->cur_count;
+  a.cur_mode = c->cur ? 1 : c->cur_mode;
   a.flags = c->flags;
   a.n_tasks = c->n_tasks;
   a.sched_len = c->sched_len;
@@ -1166,7 +1173,15 @@ void nav_fill(vn_ctx* c, EnvArgs& a) {
 // After the step's env_kernel launch (rc = its result), on the same stream.
 int nav_after_step(vn_ctx* c, const EnvArgs& a, int rc, hipStream_t stream) {
   if (rc != VN_OK || !c->nav) return rc;
-  return nav_launch(c->nav, NAV_FORM_STEP, c->recs, a.done, a.info_trunc, a.info_len, a.info_ret, stream);
+  rc = nav_launch(c->nav, NAV_FORM_STEP, c->recs, a.done, a.info_trunc, a.info_len, a.info_ret, stream);
+  if (rc != VN_OK || !c->cur || c->cur->cfg.window <= 0) return rc;
+  return cur_count_launch(c->cur, c->recs, a.done, a.info_trunc, 1, stream);
+}
+// After a launch that may have moved envs to another scene outside a step (vn_reset,
+// vn_set_state): the adaptive curriculum notes every env's scene again and counts nothing.
+int cur_refresh(vn_ctx* c, int rc, hipStream_t stream) {
+  if (rc != VN_OK || !c->cur || c->cur->cfg.window <= 0) return rc;
+  return cur_count_launch(c->cur, c->recs, nullptr, nullptr, 0, stream);
 }
 
 // Whether a launch writing to (obs, goal) may skip rows that already hold their frame. The
@@ -1287,6 +1302,7 @@ void free_ctx(vn_ctx* c) {
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   nav_destroy(c->nav);
+  cur_destroy(c->cur);
   delete c;
 }
 
@@ -1451,7 +1467,8 @@ int vn_reset(vn_ctx* c, const int32_t* env_mask_dev, vn_stream_t stream) {
   a.mask = env_mask_dev;
   const int rc = launch_env<MODE_RESET>(c, a, (hipStream_t)stream);
   if (rc != VN_OK || !c->nav) return rc;
-  return nav_launch(c->nav, NAV_FORM_RESET, c->recs, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  return cur_refresh(c, nav_launch(c->nav, NAV_FORM_RESET, c->recs, nullptr, nullptr, nullptr, nullptr,
+                                   (hipStream_t)stream), (hipStream_t)stream);
 }
 
 int vn_observe(vn_ctx* c, uint8_t* obs_dev, uint8_t* goal_dev, int32_t* state_dev, vn_stream_t stream) {
@@ -1616,6 +1633,10 @@ int vn_nav_enable(vn_ctx* c, int on) {
   }
   DeviceGuard guard(c->device);
   VN_HIP(hipDeviceSynchronize());
+  if (c->cur) {  // its tables are built from the nav tables that go away here
+    const int rc = vn_nav_curriculum(c, nullptr);
+    if (rc != VN_OK) return rc;
+  }
   nav_destroy(c->nav);
   c->nav = nullptr;
   if (!on) return VN_OK;
@@ -1710,6 +1731,99 @@ int vn_nav_set_episode_log(vn_ctx* c, const vn_episode_log* log) {
   return nav_set_episode_log(c->nav, log);
 }
 
+int vn_nav_curriculum(vn_ctx* c, const vn_geo_curriculum* cfg) {
+  if (!c) return fail(VN_EINVAL, "vn_nav_curriculum: NULL ctx");
+  if (!c->nav) return fail(VN_ESTATE, "vn_nav_curriculum: navigation info is not enabled (vn_nav_enable)");
+  if (cfg) {
+    const char* bad = nullptr;
+    if (cfg->mode != 1 && cfg->mode != 2) bad = "mode must be 1 or 2";
+    else if (cfg->level < 1) bad = "level must be >= 1";
+    else if (cfg->level_min < 1) bad = "level_min must be >= 1";
+    else if (cfg->step < 1) bad = "step must be >= 1";
+    else if (cfg->window < 0) bad = "window must be >= 0";
+    else if (!(cfg->down >= 0.0f && cfg->down < cfg->up && cfg->up <= 1.0f)) bad = "need 0 <= down < up <= 1";
+    if (bad) return fail(VN_EINVAL, std::string("vn_nav_curriculum: ") + bad);
+  }
+  DeviceGuard guard(c->device);
+  VN_HIP(hipDeviceSynchronize());
+  if (!cfg) {
+    if (!c->cur) return VN_OK;
+    VN_HIP(hipMemcpy(c->scenes, c->scenes_spd.data(), c->scenes_spd.size() * sizeof(SceneDev), hipMemcpyHostToDevice));
+    c->scenes_host = c->scenes_spd;
+    c->scenes_spd.clear();
+    cur_destroy(c->cur);
+    c->cur = nullptr;
+    return VN_OK;
+  }
+  // the new tables first: a failure below leaves the context as it was
+  std::vector<int64_t> order_off(c->n_scenes);
+  for (int k = 0; k < c->n_scenes; ++k) order_off[k] = c->scenes_host[k].spd_off;
+  CurState* cur = nullptr;
+  int rc = cur_create(&cur, c->nav, *cfg, order_off);
+  if (rc != VN_OK) return rc;
+  static_assert(sizeof(SceneDev) % 4 == 0 && offsetof(SceneDev, cur_oi) % 4 == 0, "the level is a word of the table");
+  cur->table = CurSceneTable{reinterpret_cast<int32_t*>(c->scenes), (int)(sizeof(SceneDev) / 4),
+                             (int)(offsetof(SceneDev, cur_oi) / 4)};
+  std::vector<SceneDev> sh = c->scenes_host;
+  std::vector<int32_t> st((size_t)c->n_scenes * 4);
+  hipError_t e = hipMemcpy(st.data(), cur->state, st.size() * 4, hipMemcpyDeviceToHost);
+  for (int k = 0; k < c->n_scenes; ++k) {
+    sh[k].cnt_off = cur->scenes_host[k].cnt_off;
+    sh[k].maxd = cur->scenes_host[k].D;
+    sh[k].cur_oi = st[k];
+    sh[k].cur_mode = cfg->mode;
+  }
+  if (e == hipSuccess) {
+    rc = cur_count_launch(cur, c->recs, nullptr, nullptr, 0, 0);  // ep_scene from the records
+    if (rc == VN_OK) e = hipDeviceSynchronize();
+  }
+  // the scene table last: nothing of the context has changed before this copy
+  if (e == hipSuccess && rc == VN_OK)
+    e = hipMemcpy(c->scenes, sh.data(), sh.size() * sizeof(SceneDev), hipMemcpyHostToDevice);
+  if (e != hipSuccess || rc != VN_OK) {
+    cur_destroy(cur);
+    return rc != VN_OK ? rc : hip_fail(e, "vn_nav_curriculum: enable");
+  }
+  if (c->cur) cur_destroy(c->cur);  // reconfigured: scenes_spd already holds the spd curriculum's table
+  else c->scenes_spd = c->scenes_host;
+  c->scenes_host = sh;
+  c->cur = cur;
+  return VN_OK;
+}
+
+int vn_nav_curriculum_advance(vn_ctx* c, vn_stream_t stream) {
+  if (!c) return fail(VN_EINVAL, "vn_nav_curriculum_advance: NULL ctx");
+  if (!c->cur) return fail(VN_ESTATE, "vn_nav_curriculum_advance: the geodesic curriculum is off (vn_nav_curriculum)");
+  DeviceGuard guard(c->device);
+  return cur_advance(c->cur, (hipStream_t)stream);
+}
+
+int vn_nav_curriculum_get_state(vn_ctx* c, int32_t* dst, vn_stream_t stream) {
+  if (!c || !dst) return fail(VN_EINVAL, "vn_nav_curriculum_get_state: NULL argument");
+  if (!c->cur) return fail(VN_ESTATE, "vn_nav_curriculum_get_state: the geodesic curriculum is off (vn_nav_curriculum)");
+  DeviceGuard guard(c->device);
+  return cur_get_state(c->cur, dst, (hipStream_t)stream);
+}
+
+int vn_nav_curriculum_set_state(vn_ctx* c, const int32_t* src, vn_stream_t stream) {
+  if (!c || !src) return fail(VN_EINVAL, "vn_nav_curriculum_set_state: NULL argument");
+  if (!c->cur) return fail(VN_ESTATE, "vn_nav_curriculum_set_state: the geodesic curriculum is off (vn_nav_curriculum)");
+  DeviceGuard guard(c->device);
+  return cur_set_state(c->cur, src, c->recs, (hipStream_t)stream);
+}
+
+int vn_nav_curriculum_tables(vn_ctx* c, int scene, const int32_t** order_dev, const int32_t** count_dev, int32_t* n,
+                             int32_t* D) {
+  if (!c || scene < 0 || scene >= c->n_scenes) return fail(VN_EINVAL, "vn_nav_curriculum_tables: bad args");
+  if (!c->cur) return fail(VN_ESTATE, "vn_nav_curriculum_tables: the geodesic curriculum is off (vn_nav_curriculum)");
+  const CurScene& S = c->cur->scenes_host[scene];
+  if (order_dev) *order_dev = c->cur->order + S.order_off;
+  if (count_dev) *count_dev = c->cur->count + S.cnt_off;
+  if (n) *n = S.n;
+  if (D) *D = S.D;
+  return VN_OK;
+}
+
 int vn_set_info_buffers(vn_ctx* c, float* ep_return, int32_t* ep_length, int32_t* terminal_state,
                         uint8_t* truncated, int32_t* img_row, int32_t* goal_row) {
   if (!c) return fail(VN_EINVAL, "vn_set_info_buffers: NULL ctx");
@@ -1780,6 +1894,8 @@ int vn_set_env_scenes(vn_ctx* c, const int32_t* env_scene_host) {
 int vn_set_curriculum_scenes(vn_ctx* c, double complexity, const int32_t* modes_host, const double* offsets_host) {
   if (!c || !modes_host || !offsets_host) return fail(VN_EINVAL, "vn_set_curriculum_scenes: NULL argument");
   if (!(complexity >= 0.0)) return fail(VN_EINVAL, "vn_set_curriculum: bad complexity");
+  if (c->cur)  // it would upload the spd curriculum's scene table over the geodesic one
+    return fail(VN_ESTATE, "vn_set_curriculum: the geodesic curriculum is on (vn_nav_curriculum(ctx, NULL) first)");
   int any = 0;
   for (int i = 0; i < c->n_scenes; ++i) {
     if (modes_host[i] < 0 || modes_host[i] > 2) return fail(VN_EINVAL, "vn_set_curriculum: bad mode");
@@ -1892,7 +2008,7 @@ int vn_set_state(vn_ctx* c, const int32_t* src, vn_stream_t stream) {
   hipLaunchKernelGGL(set_state_kernel, dim3((c->n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, c->recs,
                      c->n_envs, src, c->scenes, c->n_scenes, c->graph);
   VN_HIP(hipGetLastError());
-  return VN_OK;
+  return cur_refresh(c, VN_OK, (hipStream_t)stream);
 }
 
 int vn_get_episode_returns(vn_ctx* c, float* dst, vn_stream_t stream) {

@@ -120,6 +120,19 @@ class EpisodeLog(ctypes.Structure):
     ]
 
 
+class GeoCurriculum(ctypes.Structure):
+    """vn_geo_curriculum (include/vnav.h)."""
+    _fields_ = [
+        ("mode", c_int32),
+        ("level", c_int32),
+        ("level_min", c_int32),
+        ("step", c_int32),
+        ("window", c_int32),
+        ("up", c_float),
+        ("down", c_float),
+    ]
+
+
 # name -> (restype, argtypes). Every symbol here is declared in include/vnav.h.
 SIGNATURES = {
     "vn_version": (ctypes.c_char_p, []),
@@ -166,6 +179,11 @@ SIGNATURES = {
     "vn_nav_sample_episodes": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_uint32, c_void_p, c_void_p,
                                        P(c_int64), c_void_p]),
     "vn_nav_set_episode_log": (c_int, [c_void_p, P(EpisodeLog)]),
+    "vn_nav_curriculum": (c_int, [c_void_p, P(GeoCurriculum)]),
+    "vn_nav_curriculum_advance": (c_int, [c_void_p, c_void_p]),
+    "vn_nav_curriculum_get_state": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vn_nav_curriculum_set_state": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vn_nav_curriculum_tables": (c_int, [c_void_p, c_int, P(c_void_p), P(c_void_p), P(c_int32), P(c_int32)]),
 }
 
 SIGNATURES.update({

@@ -68,7 +68,7 @@ class A2CTrainer:
                  capture_collectives=False, allreduce_buckets=1, time_collectives=False, dedup_goals=None,
                  unreal=False, pc_weight=0.05, rp_weight=1.0, vr_weight=1.0, pc_gamma=0.9, unreal_envs=16,
                  unreal_source="rollout", nav_metrics=False, expert_weight=None, expert_anneal_steps=0,
-                 pg_coefficient=1.0):
+                 pg_coefficient=1.0, geo_curriculum=None):
         self.env = env
         self.lib = _lib.load()
         # check before every replayed UNREAL pass that the side stream's buffers and gradient
@@ -160,6 +160,16 @@ class A2CTrainer:
             self.expert_mask = torch.zeros((T, E), dtype=torch.uint8, **kw)
             self.expert_stats = torch.zeros(4, dtype=torch.float32, **kw)
             self.expert_steps = torch.zeros(1, dtype=torch.int64, **kw)
+        # geo_curriculum (None = off): VectorEnv.set_geodesic_curriculum's keyword arguments. Starts
+        # are drawn within `level` actions of the goal, and with window > 0 every update ends its
+        # rollout with one curriculum_advance(), inside the captured graph too: the level moves on
+        # the device, so the graph stays valid. Enabled here, before any capture and after the nav
+        # setup above (set_nav_info would switch it off). At world > 1 every rank adapts on its own
+        # envs, with no collective: curriculum_level is this rank's mean over scenes.
+        self.geo_curriculum = None if geo_curriculum is None else dict(geo_curriculum)
+        if self.geo_curriculum is not None:
+            env.set_geodesic_curriculum(**self.geo_curriculum)
+            self.cur_state = torch.zeros((4, len(env.scenes)), dtype=torch.int32, **kw)
         # device schedule: [next sampling-counter base (updates * T), env-steps so far, this
         # update's counter base] and the learning rate of the update (vn_a2c_schedule)
         self.sched = torch.zeros(3, dtype=torch.int64, **kw)
@@ -1008,6 +1018,9 @@ class A2CTrainer:
         """rollout + update; returns the device metric vector [value_loss, action_loss,
         entropy, return mean, grad norm, aux loss, episodes, return sum, length sum]."""
         batch, _ = self.sample_training_batch()
+        if self.geo_curriculum is not None:  # the rollout's episodes decide the next rollout's level
+            self.env.curriculum_advance()
+            self.env.curriculum_state(out=self.cur_state)
         self.update(batch)
         N = self.num_steps * self.env.num_envs
         # [stats / N, grad norm, aux loss (sum of the per-head MSEs, trainer.py:51-54),
@@ -1030,6 +1043,8 @@ class A2CTrainer:
         if self.expert:  # then the three expert sums, summed over ranks too, and the weight used
             m = torch.cat([m, vdist.reduce_metrics_(self.expert_stats[:3].clone(), 0, self.group),
                            self.expert_stats[3:]])
+        if self.geo_curriculum is not None:  # this rank's mean level over scenes, in the same fetch
+            m = torch.cat([m, self.cur_state[0].to(torch.float32).mean().reshape(1)])
         return m
 
     def _graph_update(self):
@@ -1080,6 +1095,8 @@ class A2CTrainer:
             expert = {"expert_loss": nlq / valid if valid else float("nan"),
                       "expert_agreement": agree / valid if valid else float("nan"), "expert_weight": w}
             expert_term = w * nlq / (N * self.world)  # w * expert_loss * valid / N
+            k += 4
+        cur = {"curriculum_level": vals[k]} if self.geo_curriculum is not None else {}
         dt = time.perf_counter() - t0
         return {
             "step": self.total_steps, "updates": self.num_updates,
@@ -1095,6 +1112,7 @@ class A2CTrainer:
             **unreal,
             **nav,
             **expert,
+            **cur,
         }
 
     def run(self, log_every=10, logger=print):
@@ -1114,6 +1132,8 @@ class A2CTrainer:
         expert term on also ``expert_agreement``, the share of the labelled samples whose
         sampled action starts a shortest path."""
         saved_sched = self.sched.clone()  # sampling counter and step count: evaluation leaves both
+        # the curriculum's counters see the rollouts below: levels, counters back afterwards
+        saved_cur = self.env.curriculum_state().clone() if self.geo_curriculum is not None else None
         E, T = self.env.num_envs, self.num_steps
         tot = torch.zeros(7 if self.nav_metrics else 3, dtype=torch.float64)
         agree = torch.zeros(2, dtype=torch.float64)  # agreeing, labelled samples
@@ -1134,6 +1154,8 @@ class A2CTrainer:
             if tot[0] >= episodes:
                 break
         self.sched.copy_(saved_sched)
+        if saved_cur is not None:
+            self.env.set_curriculum_state(saved_cur)
         n, rsum, lsum = tot.tolist()[:3]
         out = {"episodes": n, "reward": rsum / n if n else float("nan"),
                "episode_length": lsum / n if n else float("nan")}
@@ -1263,6 +1285,8 @@ class A2CTrainer:
                      nav_stats=self.nav_stats.clone())
         if self.recurrent:
             saved["carry"] = {k: getattr(self, k).clone() for k in self._RECURRENT_STATE}
+        if self.geo_curriculum is not None:
+            saved["cur"] = env.curriculum_state().clone()
         try:
             env.set_env_scenes(env_scenes)
             env.set_max_episode_steps(limit)
@@ -1303,6 +1327,8 @@ class A2CTrainer:
             env.set_state(saved["state"])
             env.set_episode_returns(saved["returns"])
             env.set_nav_state(saved["nav"])
+            if "cur" in saved:  # after set_state: it notes the restored envs' scenes
+                env.set_curriculum_state(saved["cur"])
             env.nav_episode_stats()  # the per-env accumulators of the surplus episodes: dropped
             env.refresh_nav_outputs()
             env.observe(gather=False)
@@ -1325,6 +1351,8 @@ class A2CTrainer:
                 sd[k] = getattr(self, k).cpu()
         if self.nav_metrics:  # start distance and length offset of the running episodes
             sd["env_nav"] = self.env.get_nav_state().cpu()
+        if self.geo_curriculum is not None:  # per scene: level and the running window's counters
+            sd["env_curriculum"] = self.env.curriculum_state().cpu()
         if self.replay:  # the replay ring and its draw stream resume exactly
             sd["replay_rows"] = self.replay_rows.cpu()
             sd["replay_meta"] = self.replay_meta.cpu()  # next slot, filled, draw counter, drawn slot
@@ -1374,6 +1402,15 @@ class A2CTrainer:
                 warnings.warn("checkpoint holds no navigation state (saved without nav_metrics): the running "
                               "episodes are measured from their current positions")
                 self.env.set_nav_info(True)
+                if self.geo_curriculum is not None:  # set_nav_info switched it off
+                    self.env.set_geodesic_curriculum(**self.geo_curriculum)
+        if self.geo_curriculum is not None:
+            if "env_curriculum" in sd:
+                self.env.set_curriculum_state(sd["env_curriculum"].to(self.device))
+            else:
+                warnings.warn("checkpoint holds no curriculum state (saved without geo_curriculum): every scene "
+                              "starts from the configured level")
+                self.env.set_geodesic_curriculum(**self.geo_curriculum)
         if self.expert:  # the env's own mask buffer = the restored states' masks (the next rollout's slot 0)
             self.env.refresh_nav_outputs()
         self.num_updates = int(sd["num_updates"])

@@ -145,6 +145,7 @@ class VectorEnv:
         self._ctx = handle
         self.nav_info = False
         self.episode_log = None
+        self.geo_curriculum = None  # set_geodesic_curriculum's configuration while it is on
         # the env -> scene assignment (vn_set_env_scenes; the native default)
         self.env_scenes = np.arange(self.num_envs, dtype=np.int32) % len(self.scenes)
         # bumped by every call that replaces the kernels' per-ctx configuration (tables,
@@ -247,6 +248,7 @@ class VectorEnv:
             self._info.pop(k, None)
         self.nav_info = False
         self.episode_log = None  # the log lives in the nav state
+        self.geo_curriculum = None  # vn_nav_enable switches the geodesic curriculum off first
         _lib.check(self.lib.vn_nav_enable(self._ctx, 1 if on else 0), "vn_nav_enable")
         if not on:
             return
@@ -374,6 +376,92 @@ class VectorEnv:
         self.episode_log = log
         return log
 
+    # -- geodesic curriculum (DESIGN.md "Geodesic curriculum") ------------------
+    def set_geodesic_curriculum(self, level=1, mode=1, window=0, up=0.8, down=0.3, step=1, level_min=1):
+        """Draw every reset's start among the states within ``level`` actions of the goal
+        (0 < distance_to_goal <= level; vn_nav_curriculum), the unit of ``distance_to_goal``,
+        SPL and the EpisodeSet buckets. mode 1: uniform over them; mode 2: with probability 0.9
+        among them and 0.1 among the farther states. ``window`` > 0 makes the level adaptive, per
+        scene and on the device: once ``window`` episodes of a scene have finished,
+        ``curriculum_advance()`` raises its level by ``step`` if their success rate is >= ``up``
+        and lowers it (not below ``level_min``) if it is <= ``down``; levels stay within the
+        scene's largest distance. ``level=None`` switches it off and restores the starts there
+        were before (a ``set_complexity`` curriculum included). Turns ``nav_info`` on if it was
+        off; a captured graph must be recaptured after this call, but not when the level moves.
+        Costs N^2 int32 of device memory per scene, as ``set_complexity``'s table does."""
+        self.config_generation += 1
+        if level is None:
+            if self.geo_curriculum is not None:
+                _lib.check(self.lib.vn_nav_curriculum(self._ctx, None), "vn_nav_curriculum")
+            self.geo_curriculum = None
+            return
+        cfg = dict(mode=int(mode), level=int(level), level_min=int(level_min), step=int(step), window=int(window),
+                   up=float(up), down=float(down))
+        if not self.nav_info:
+            self.set_nav_info(True)
+        c = _lib.GeoCurriculum(**cfg)
+        _lib.check(self.lib.vn_nav_curriculum(self._ctx, ctypes.byref(c)), "vn_nav_curriculum")
+        self.geo_curriculum = cfg
+
+    def _need_curriculum(self):
+        if self.geo_curriculum is None:
+            raise _lib.VnavError("the geodesic curriculum is off: set_geodesic_curriculum(level, ...)")
+
+    def curriculum_advance(self):
+        """One level decision per scene whose window is full (vn_nav_curriculum_advance): one
+        small launch on the current stream, no host value, so it may be captured in a graph.
+        Nothing is launched with ``window=0``."""
+        self._need_curriculum()
+        _lib.check(self.lib.vn_nav_curriculum_advance(self._ctx, self._stream()), "vn_nav_curriculum_advance")
+
+    def curriculum_state(self, out=None):
+        """int32 [4, S] device tensor: per scene the level, the finished episodes and successes
+        of the running window, and the scene's largest distance D."""
+        self._need_curriculum()
+        S = len(self.scenes)
+        if out is None:
+            out = torch.empty((4, S), dtype=torch.int32, device=self.device)
+        else:
+            self._check_out("curriculum state", out, torch.int32, 4 * S)
+        _lib.check(self.lib.vn_nav_curriculum_get_state(self._ctx, _lib.ptr(out), self._stream()),
+                   "vn_nav_curriculum_get_state")
+        return out
+
+    def set_curriculum_state(self, t):
+        """Restore curriculum_state()'s table (rows level, done, succ; D is the scenes' own):
+        an int32 [4, S] tensor on the env's device. Call it after set_state()."""
+        self._need_curriculum()
+        S = len(self.scenes)
+        if not isinstance(t, torch.Tensor) or t.device != self.device:
+            raise ValueError("curriculum state must be a tensor on %s" % (self.device,))
+        if t.dtype != torch.int32 or tuple(t.shape) != (4, S):
+            raise ValueError("curriculum state must be int32 [4, %d], got %s %s" % (S, t.dtype, tuple(t.shape)))
+        t = t.contiguous()
+        _lib.check(self.lib.vn_nav_curriculum_set_state(self._ctx, _lib.ptr(t), self._stream()),
+                   "vn_nav_curriculum_set_state")
+        t.record_stream(torch.cuda.current_stream(self.device))
+
+    def curriculum_tables(self, scene_index):
+        """(order int32 [N, N], count int32 [N, D + 2]) of a scene, indexed by goal (copies):
+        the states sorted stably by distance to the goal, and the number of states per goal with
+        clamp(distance, -1, D) + 1 <= b."""
+        self._need_curriculum()
+        po, pc, n, D = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(self.lib.vn_nav_curriculum_tables(self._ctx, int(scene_index), ctypes.byref(po), ctypes.byref(pc),
+                                                     ctypes.byref(n), ctypes.byref(D)), "vn_nav_curriculum_tables")
+        out = []
+        for p, cols in ((po, n.value), (pc, D.value + 2)):
+            t = torch.empty((n.value, cols), dtype=torch.int32, device=self.device)
+            # a scene's block is only 4-byte aligned: rows the copy would move as 16-byte
+            # lanes from such a base go element by element instead
+            per = cols if (p.value % 16 == 0 or (4 * cols) % 16 != 0) else 1
+            rows = torch.arange(n.value * cols // per, dtype=torch.int32, device=self.device)
+            _lib.check(self.lib.vn_gather_rows(p, 4 * per, _lib.ptr(rows), rows.numel(), _lib.ptr(t), self._stream()),
+                       "vn_gather_rows")
+            rows.record_stream(torch.cuda.current_stream(self.device))
+            out.append(t)
+        return tuple(out)
+
     # -- configuration -------------------------------------------------------
     def set_max_episode_steps(self, n):
         self.max_episode_steps = int(n or 0)
@@ -415,6 +503,8 @@ class VectorEnv:
         experiments/thor_cached_auxiliary.py:68-70): subsequent resets draw starts near the
         goal on the device (vn_set_curriculum); None switches back to uniform starts.
         mode/offset default to each scene's own semantics (Scene.curriculum)."""
+        if self.geo_curriculum is not None:
+            raise _lib.VnavError("set_complexity: the geodesic curriculum is on (set_geodesic_curriculum(None) first)")
         self.complexity = complexity
         self.config_generation += 1
         if complexity is None:

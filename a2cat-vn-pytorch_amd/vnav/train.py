@@ -122,6 +122,9 @@ class Experiment:
     expert_weight = None
     expert_anneal_steps = 0
     pg_coefficient = 1.0
+    # the geodesic start curriculum (A2CTrainer geo_curriculum): None = off, else the keyword
+    # arguments of VectorEnv.set_geodesic_curriculum (level, mode, window, up, down, step, level_min)
+    geo_curriculum = None
 
     def __init__(self, env_kwargs=None, model_kwargs=None, save_dir=None, seed=0, device=None, logger=print,
                  **overrides):
@@ -161,7 +164,7 @@ class Experiment:
                           cuda_graph=self.cuda_graph and (self.world == 1 or self.capture_collectives),
                           capture_collectives=self.capture_collectives, nav_metrics=self.nav_metrics,
                           expert_weight=self.expert_weight, expert_anneal_steps=self.expert_anneal_steps,
-                          pg_coefficient=self.pg_coefficient)
+                          pg_coefficient=self.pg_coefficient, geo_curriculum=self.geo_curriculum)
 
     def _setup(self):
         if self.trainer is None:
@@ -511,7 +514,22 @@ def main(argv=None):
                    help="anneal the expert weight linearly to 0 over STEPS env-steps (default: constant)")
     p.add_argument("--imitation", action="store_true",
                    help="imitation only: policy-gradient coefficient 0 (--expert-weight defaults to 1.0)")
+    p.add_argument("--geo-curriculum", type=int, default=None, metavar="LEVEL",
+                   help="draw every start within LEVEL actions of the goal (geodesic start curriculum)")
+    p.add_argument("--cur-window", type=int, default=None, metavar="N",
+                   help="adapt the level on the device every N finished episodes per scene (default 0: fixed level)")
+    p.add_argument("--cur-up", type=float, default=None, metavar="P", help="raise the level at a success rate >= P")
+    p.add_argument("--cur-down", type=float, default=None, metavar="Q", help="lower the level at a success rate <= Q")
+    p.add_argument("--cur-step", type=int, default=None, metavar="K", help="actions the level moves by")
+    p.add_argument("--cur-min", type=int, default=None, metavar="L", help="the lowest level")
+    p.add_argument("--cur-mode", type=int, default=None, choices=(1, 2),
+                   help="1: starts only within the level; 2: 0.9 within it, 0.1 farther")
     a = p.parse_args(argv)
+    cur = dict(window=a.cur_window, up=a.cur_up, down=a.cur_down, step=a.cur_step, level_min=a.cur_min,
+               mode=a.cur_mode)
+    cur = {k: v for k, v in cur.items() if v is not None}
+    if cur and a.geo_curriculum is None:
+        p.error("--cur-window / --cur-up / --cur-down / --cur-step / --cur-min / --cur-mode need --geo-curriculum")
     vdist.init_distributed()
     env_kwargs = {}
     if a.envs:
@@ -540,6 +558,8 @@ def main(argv=None):
         if a.expert_weight is None:
             p.error("--expert-anneal needs --expert-weight (or --imitation)")
         over["expert_anneal_steps"] = a.expert_anneal
+    if a.geo_curriculum is not None:
+        over["geo_curriculum"] = dict(cur, level=a.geo_curriculum)
     exp = make_trainer(a.name, env_kwargs=env_kwargs, save_dir=a.save_dir, seed=a.seed, **over)
     fixed = a.eval_episodes is not None or a.eval_set is not None
     if not fixed and (a.eval_buckets or a.greedy or a.save_eval_set or a.eval_max_steps is not None):

@@ -413,6 +413,54 @@ typedef struct vn_episode_log {
 } vn_episode_log;
 int vn_nav_set_episode_log(vn_ctx* ctx, const vn_episode_log* log);
 
+/* Geodesic start curriculum (DESIGN.md "Geodesic curriculum"): resets draw the start among the
+ * states within `level` actions of the goal, in the unit of geo_dist and SPL, and the level
+ * moves with the measured success rate on the device.
+ * vn_nav_curriculum(cfg) builds, per scene and on the device, from the geodesic table: D = its
+ * largest entry, key(g, s) = clamp(geo[g][s], -1, D) + 1, order[g][] = the states sorted stably
+ * by key (equal keys in ascending state order), count[g][b] = #states with key <= b for
+ * b < D + 2. Resets then draw from these tables exactly as vn_set_curriculum's draw does from
+ * its own: near set 0 < geo <= level; mode 1 uniform over it; mode 2 with probability 0.9 over it
+ * and 0.1 over the farther states; an empty near set falls to the farther ones, then to the
+ * rejection loop. The env kernels are unchanged. Costs n^2 int32 per scene for the order table
+ * (what vn_set_curriculum's table costs) plus n (D + 2) for the counts; any D the nav tables
+ * can hold is accepted. cfg = NULL switches it off and restores what was there before bit for
+ * bit: a vn_set_curriculum that was active is active again with its threshold, otherwise
+ * starts are uniform. Calling it again replaces the configuration and restarts levels and
+ * counters. Synchronises and replaces launch arguments (a captured graph must be recaptured).
+ * VN_ESTATE before vn_nav_enable. VN_EINVAL: mode not 1 or 2, level < 1, level_min < 1,
+ * step < 1, window < 0, or not 0 <= down < up <= 1. VN_ENOMEM with everything freed. Every
+ * refusal leaves the context as it was. While it is on, vn_set_curriculum* return VN_ESTATE;
+ * vn_nav_enable (either way) first switches it off.
+ * Per scene the state is int32 level, done, succ; per env ep_scene, the scene of the running
+ * episode. While window > 0 every vn_step* launches one more small kernel behind the nav
+ * launch: an env with done adds 1 to done[ep_scene[e]], and to succ[ep_scene[e]] unless
+ * truncated; then ep_scene[e] = the env's scene. vn_reset and vn_set_state launch its refresh
+ * form (ep_scene only). With window == 0 no launch is added anywhere. */
+typedef struct vn_geo_curriculum {
+  int32_t mode;      /* 1 uniform over 0 < geo <= level, 2 the 0.9 / 0.1 split */
+  int32_t level;     /* start level, clamped per scene to [min(level_min, D), D] */
+  int32_t level_min; /* >= 1 */
+  int32_t step;      /* >= 1 */
+  int32_t window;    /* finished episodes per decision; 0 = fixed level */
+  float up, down;    /* 0 <= down < up <= 1 */
+} vn_geo_curriculum;
+int vn_nav_curriculum(vn_ctx* ctx, const vn_geo_curriculum* cfg);
+/* One small launch on `stream`, no host value: capturable, and a captured update stays valid
+ * while the level moves. For every scene with done >= window: r = (float)succ / (float)done
+ * (one fp32 division); r >= up: level = min(level + step, D); else r <= down: level =
+ * max(level - step, min(level_min, D)); then done = succ = 0 and the scene's threshold takes
+ * the level. window == 0: launches nothing, VN_OK. VN_ESTATE while the curriculum is off. */
+int vn_nav_curriculum_advance(vn_ctx* ctx, vn_stream_t stream);
+/* [4][n_scenes] int32 on the device: level, done, succ, D. Stream-ordered. set_state takes rows
+ * 0..2 (row 3 is ignored), holds each level to [min(level_min, D), D], writes the scenes'
+ * thresholds and sets ep_scene from the env records: call it after vn_set_state. */
+int vn_nav_curriculum_get_state(vn_ctx* ctx, int32_t* dst_dev_4xS, vn_stream_t stream);
+int vn_nav_curriculum_set_state(vn_ctx* ctx, const int32_t* src_dev_4xS, vn_stream_t stream);
+/* The scene's tables on the device: order [n][n], count [n][D + 2], both indexed by goal. */
+int vn_nav_curriculum_tables(vn_ctx* ctx, int scene, const int32_t** order_dev, const int32_t** count_dev,
+                             int32_t* n, int32_t* D);
+
 /* Scene-cache arena: all scenes' frames back to back, row = frame. */
 int vn_frame_arena(vn_ctx* ctx, const uint8_t** arena_dev, int64_t* frame_bytes,
                    int64_t* n_rows);
