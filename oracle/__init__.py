@@ -30,5 +30,8 @@ Modules
   aux_head_cases.py  case tables of the aux deconv head tests, the launch rules (samples per
               item, bands, persistent grids, the finish kernel's lanes, the two-stage reduce) that
               place them, seeded inputs and the float64 restatement of the heads and their checks
+  goal_trunk_cases.py  the goal trunk's launch regimes above 16 rows at the three geometries (the
+              split-K / slab / lane rules of unreal_head_cases.py on its shapes, the persistent kernels'
+              band structs restated), the switches in n and a smallest case list around them
   update_checks.py  one A2CTrainer update restated in float64, the UNREAL terms included
 """

@@ -6,7 +6,9 @@ envs, float frames, other action counts) hold the kernels to the same bars with 
 code: the error measures, the reading of the activation store the forward wrote, the ReLU
 masks of the GPU forward (the oracle is run with them, see GoalNetOracle.forward_masked, and
 every disagreeing bit is asserted to be a tie), the comparison of the 14 (+ aux) parameter
-gradients, and the recurrent core against torch's float64 nn.LSTM (lstm_core_check). The
+gradients, the whole forward + backward of the goal trunk on u8 frames (trunk_heads_u8_vs_oracle,
+which tests/test_goal_trunk_regimes_gpu.py runs at every launch regime above 16 rows), and the
+recurrent core against torch's float64 nn.LSTM (lstm_core_check). The
 BigHouse trunk's twins (_bighouse_masks, _bighouse_forward_masked, _ties_only,
 _bighouse_grads_vs_oracle) serve tests/test_bighouse_regimes_gpu.py and oracle/update_checks.py.
 
@@ -21,7 +23,7 @@ import numpy as np
 import torch
 
 from oracle import a2c as oa2c
-from oracle.policy import trunk_sizes
+from oracle.policy import GoalNetOracle, frames_to_float, trunk_sizes
 
 NAMES = {"shared_base.0.0": "conv1", "shared_base.0.2": "conv2", "conv_base.0.0": "conv3",
          "conv_base.0.2": "conv4", "conv_merge.0.1": "fc", "policy_logits.0": "policy_logits",
@@ -187,6 +189,81 @@ def _grads_vs_oracle(net, grads, ref, heads=None, tol=1e-4):
     bad = {k: "%.3g" % e for k, e in errs.items() if e > tol}
     assert not bad, bad
     return max(errs.values())
+
+
+NAN_BITS = 0x7FC5A5A5  # a quiet NaN with a payload (as int32): few_env_cases.GUARD_BITS
+
+
+def _nhwc(t):
+    return t.detach().permute(0, 2, 3, 1).numpy()
+
+
+def trunk_heads_u8_vs_oracle(tag, pol, frames, img, gl, n, A, actions, rets, nan_fill=False):
+    """Forward + backward of n samples of u8 frames through pol.net (the goal trunk and its heads)
+    against GoalNetOracle in float64 under the GPU's own ReLU masks: logits, value, X1..X5 and all
+    14 parameter gradients of the A2C loss, at the project's bars (module text); every mask bit that
+    disagrees with the oracle's sign is asserted to be a tie. The body of tests/test_few_env_gpu.py
+    test_trunk_and_heads_u8_vs_fp64_oracle, shared with tests/test_goal_trunk_regimes_gpu.py.
+
+    frames: the vn_frames handed to the kernels (dense or row-gathered); img, gl: the same frames
+    per sample, uint8 [n, H, W, 3] on the CPU; actions int32 [n], rets float32 [n] on the CPU.
+    The activation store is prefilled with NaN. nan_fill: so are the workspace and grads, with a
+    NaN bit pattern: vn_policy_backward overwrites grads (include/vnav.h) and the workspace is
+    scratch it owns, so a block of either that a launch regime leaves unwritten shows as NaN in a
+    gradient. Returns the errors by name (outputs, activations, the 14 gradient tensors)."""
+    hw = tuple(pol.net.frame_hw)
+    net, params = pol.net, pol.params.data
+    acts = net.new_acts(n)
+    acts.fill_(float("nan"))
+    out = torch.zeros((n, 8), device="cuda")
+    net.forward(params, frames, n, acts, n, 0, out)
+    masks = _gpu_masks(net, acts, n)  # before the backward: it overwrites X1
+    v = _acts_views(net, acts, n)
+    x1, x2, x3, x4, x5 = (v["X%d" % i].cpu().numpy() for i in range(1, 6))
+    dout = a2c_loss_grad(out, actions.cuda(), rets.cuda(), A)
+    grads = torch.zeros_like(params)
+    ws = torch.empty(net.workspace_floats(n), device="cuda")
+    if nan_fill:
+        grads.view(torch.int32).fill_(NAN_BITS)
+        ws.view(torch.int32).fill_(NAN_BITS)
+    net.backward(params, frames, n, acts, n, dout, grads, ws)
+    torch.cuda.synchronize()
+
+    ref = GoalNetOracle(hw, 3, A).load_reference(pol.reference_state_dict()).double()
+    logits, value, rx4, pre = ref.forward_masked(frames_to_float(img).double(), frames_to_float(gl).double(), masks)
+    flips = _check_masks_are_signs(masks, pre)
+    o = out.cpu().numpy()
+    elem = _check_outputs(o[:, :A], o[:, A], logits.detach().numpy(), value.detach().numpy().ravel())
+    e = {"logits": _err(o[:, :A], logits.detach().numpy()), "value": _err(o[:, A], value.detach().numpy().ravel()),
+         "X1": max(_err(x1[:, 0], _nhwc(pre["z1i"] * masks["m1i"])), _err(x1[:, 1], _nhwc(pre["z1g"] * masks["m1g"]))),
+         "X2": max(_err(x2[:, 0], _nhwc(pre["z2i"] * masks["m2i"])), _err(x2[:, 1], _nhwc(pre["z2g"] * masks["m2g"]))),
+         "X3": _err(x3, _nhwc(pre["z3"] * masks["m3"])), "X4": _err(x4, _nhwc(rx4)),
+         "X5": _err(x5, (pre["z5"] * masks["m5"]).detach().numpy())}
+    print("%s %s n=%d A=%d: %s; elementwise %.3g / %.3g of the bound; tie flips %s"
+          % (tag, "%dx%d" % hw, n, A, " ".join("%s %.3g" % kv for kv in e.items()), elem[0], elem[1], flips))
+    bad = {k: "%.3g" % x for k, x in e.items() if not x <= 1e-5}
+    assert not bad, bad
+    loss, _ = oa2c.loss(logits, value.view(-1), actions.long(), rets.double())
+    loss.backward()
+    g = _grad_errs(net, grads, ref)
+    print("%s %s n=%d A=%d: worst gradient error %.3g of scale (%s)"
+          % (tag, "%dx%d" % hw, n, A, max(g.values()), max(g, key=g.get)))
+    assert len(g) == 14
+    bad = {k: "%.3g" % x for k, x in g.items() if not x <= 1e-4}
+    assert not bad, bad
+    e.update(g)
+    return e
+
+
+def _grad_errs(net, grads, ref):
+    """The 14 trunk + head gradient tensors by reference name -> {name: error of its scale}."""
+    mine = net.to_reference(grads)
+    errs = {}
+    for k, attr in NAMES.items():
+        mod = getattr(ref, attr)
+        for kind in ("weight", "bias"):
+            errs[k + "." + kind] = _err(mine[k + "." + kind].numpy(), getattr(mod, kind).grad.numpy())
+    return errs
 
 
 def a2c_loss_grad(out, actions, rets, num_actions=4):

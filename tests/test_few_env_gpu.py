@@ -19,11 +19,10 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import a2c as oa2c
 from oracle import few_env_cases as fc
 from oracle.policy import GoalNetOracle, frames_to_float
 from oracle.trunk_checks import (_acts_views, _check_masks_are_signs, _check_outputs, _err, _gpu_masks,
-                                 _grads_vs_oracle, a2c_loss_grad, lstm_core_check)
+                                 _grads_vs_oracle, lstm_core_check, trunk_heads_u8_vs_oracle)
 
 pytestmark = pytest.mark.gpu
 
@@ -38,53 +37,20 @@ def _noisy_policy(hw, A, seed):
     return pol
 
 
-def _nhwc(t):
-    return t.permute(0, 2, 3, 1).numpy()
-
-
 @pytest.mark.parametrize("hw,n,A", fc.TRUNK_CASES, ids=fc.TRUNK_IDS)
 def test_trunk_and_heads_u8_vs_fp64_oracle(hw, n, A):
-    """A: forward + backward of n samples of u8 frames: logits, value, X3 / X4 (conv34_small_kernel
-    below 17 samples), X5 (conv_merge: skinny_kernel) and all 14 parameter gradients of the A2C
-    loss. n walks the row instances of launch_skinny on both sides of each switch and the switch
-    to the tensor-core path; odd n leaves conv34_small's last workgroup one live row; 300x400
-    runs conv_merge's K = 12512 in several LDS chunks plus a remainder."""
+    """A: forward + backward of n samples of u8 frames: logits, value, X1 / X2 (the persistent conv1
+    and conv2 forwards), X3 / X4 (conv34_small_kernel below 17 samples), X5 (conv_merge:
+    skinny_kernel) and all 14 parameter gradients of the A2C loss (oracle/trunk_checks.py
+    trunk_heads_u8_vs_oracle). n walks the row instances of launch_skinny on both sides of each
+    switch and the switch to the tensor-core path; odd n leaves conv34_small's last workgroup one
+    live row; 300x400 runs conv_merge's K = 12512 in several LDS chunks plus a remainder."""
     from vnav.policy import frames_from_batch
     pol = _noisy_policy(hw, A, fc.weight_seed(hw, n, A))
-    net, params = pol.net, pol.params.data
     img, gl = (torch.as_tensor(f) for f in fc.u8_frames(hw, n))
     actions, rets = (torch.as_tensor(v) for v in fc.loss_inputs(n, A))
     img_d, gl_d = img.cuda(), gl.cuda()
-    frames = frames_from_batch(img_d, gl_d)
-    acts = net.new_acts(n)
-    acts.fill_(float("nan"))
-    out = torch.zeros((n, 8), device="cuda")
-    net.forward(params, frames, n, acts, n, 0, out)
-    masks = _gpu_masks(net, acts, n)  # before the backward: it overwrites X1
-    v = _acts_views(net, acts, n)
-    x3, x4, x5 = v["X3"].cpu().numpy(), v["X4"].cpu().numpy(), v["X5"].cpu().numpy()
-    dout = a2c_loss_grad(out, actions.cuda(), rets.cuda(), A)
-    grads = torch.zeros_like(params)
-    ws = torch.empty(net.workspace_floats(n), device="cuda")
-    net.backward(params, frames, n, acts, n, dout, grads, ws)
-    torch.cuda.synchronize()
-
-    ref = GoalNetOracle(hw, 3, A).load_reference(pol.reference_state_dict()).double()
-    logits, value, rx4, pre = ref.forward_masked(frames_to_float(img).double(), frames_to_float(gl).double(), masks)
-    flips = _check_masks_are_signs(masks, pre)
-    o = out.cpu().numpy()
-    _check_outputs(o[:, :A], o[:, A], logits.detach().numpy(), value.detach().numpy().ravel())
-    e = {"logits": _err(o[:, :A], logits.detach().numpy()), "value": _err(o[:, A], value.detach().numpy().ravel()),
-         "X3": _err(x3, _nhwc((pre["z3"] * masks["m3"]).detach())), "X4": _err(x4, _nhwc(rx4.detach())),
-         "X5": _err(x5, (pre["z5"] * masks["m5"]).detach().numpy())}
-    print("few-env A %s n=%d A=%d: %s; tie flips %s" % (fc.GEO_IDS[hw], n, A,
-                                                       " ".join("%s %.3g" % kv for kv in e.items()), flips))
-    bad = {k: "%.3g" % x for k, x in e.items() if not x <= 1e-5}
-    assert not bad, bad
-    loss, _ = oa2c.loss(logits, value.view(-1), actions.long(), rets.double())
-    loss.backward()
-    worst = _grads_vs_oracle(net, grads, ref)
-    print("few-env A %s n=%d A=%d: worst gradient error %.3g of scale" % (fc.GEO_IDS[hw], n, A, worst))
+    trunk_heads_u8_vs_oracle("few-env A", pol, frames_from_batch(img_d, gl_d), img, gl, n, A, actions, rets)
 
 
 @pytest.mark.parametrize("hw,n", fc.GUARD_CASES, ids=fc.GUARD_IDS)
