@@ -38,6 +38,7 @@
 #include "vn_common.h"
 #include "vn_curriculum.h"
 #include "vn_nav.h"
+#include "vn_shaping.h"
 #include "vn_unit_float.h"
 
 namespace vn {
@@ -1111,6 +1112,8 @@ struct vn_ctx {
   // (cnt_off, maxd, cur_oi, cur_mode of the spd curriculum) for switching it off again
   CurState* cur = nullptr;
   std::vector<SceneDev> scenes_spd;
+  // vn_nav_progress: the per-env progress record and its outputs (vn_shaping.hip)
+  ShapeState* shape = nullptr;
 };
 
 namespace {
@@ -1169,13 +1172,22 @@ void nav_fill(vn_ctx* c, EnvArgs& a) {
   if (!a.info_trunc) a.info_trunc = c->nav->s_trunc;
   if (!a.info_len) a.info_len = c->nav->s_len;
   if (c->nav->log.capacity > 0 && !a.info_ret) a.info_ret = c->nav->s_ret;
+  if (c->shape && !a.info_term) a.info_term = c->shape->s_term;  // the progress kernel reads it
 }
 // After the step's env_kernel launch (rc = its result), on the same stream.
 int nav_after_step(vn_ctx* c, const EnvArgs& a, int rc, hipStream_t stream) {
   if (rc != VN_OK || !c->nav) return rc;
   rc = nav_launch(c->nav, NAV_FORM_STEP, c->recs, a.done, a.info_trunc, a.info_len, a.info_ret, stream);
+  if (rc == VN_OK && c->shape)
+    rc = shape_launch(c->shape, c->nav, SHAPE_FORM_STEP, c->recs, nullptr, a.done, a.info_trunc, a.info_term, stream);
   if (rc != VN_OK || !c->cur || c->cur->cfg.window <= 0) return rc;
   return cur_count_launch(c->cur, c->recs, a.done, a.info_trunc, 1, stream);
+}
+// The progress record of the envs a launch outside a step may have moved (vn_reset: the masked
+// ones; vn_set_state: all), from their records.
+int shape_refresh(vn_ctx* c, int rc, const int32_t* mask, hipStream_t stream) {
+  if (rc != VN_OK || !c->shape) return rc;
+  return shape_launch(c->shape, c->nav, SHAPE_FORM_REFRESH, c->recs, mask, nullptr, nullptr, nullptr, stream);
 }
 // After a launch that may have moved envs to another scene outside a step (vn_reset,
 // vn_set_state): the adaptive curriculum notes every env's scene again and counts nothing.
@@ -1303,6 +1315,7 @@ void free_ctx(vn_ctx* c) {
     if (p) (void)hipFree(p);
   nav_destroy(c->nav);
   cur_destroy(c->cur);
+  shape_destroy(c->shape);
   delete c;
 }
 
@@ -1467,8 +1480,9 @@ int vn_reset(vn_ctx* c, const int32_t* env_mask_dev, vn_stream_t stream) {
   a.mask = env_mask_dev;
   const int rc = launch_env<MODE_RESET>(c, a, (hipStream_t)stream);
   if (rc != VN_OK || !c->nav) return rc;
-  return cur_refresh(c, nav_launch(c->nav, NAV_FORM_RESET, c->recs, nullptr, nullptr, nullptr, nullptr,
-                                   (hipStream_t)stream), (hipStream_t)stream);
+  return cur_refresh(c, shape_refresh(c, nav_launch(c->nav, NAV_FORM_RESET, c->recs, nullptr, nullptr, nullptr,
+                                                    nullptr, (hipStream_t)stream),
+                                      env_mask_dev, (hipStream_t)stream), (hipStream_t)stream);
 }
 
 int vn_observe(vn_ctx* c, uint8_t* obs_dev, uint8_t* goal_dev, int32_t* state_dev, vn_stream_t stream) {
@@ -1637,6 +1651,8 @@ int vn_nav_enable(vn_ctx* c, int on) {
     const int rc = vn_nav_curriculum(c, nullptr);
     if (rc != VN_OK) return rc;
   }
+  shape_destroy(c->shape);  // its lookups read the nav tables that go away here
+  c->shape = nullptr;
   nav_destroy(c->nav);
   c->nav = nullptr;
   if (!on) return VN_OK;
@@ -1705,6 +1721,56 @@ int vn_set_nav_state(vn_ctx* c, const int32_t* src, vn_stream_t stream) {
   if (!c->nav) return fail(VN_ESTATE, "vn_set_nav_state: navigation info is not enabled (vn_nav_enable)");
   DeviceGuard guard(c->device);
   VN_HIP(hipMemcpyAsync(c->nav->rec, src, (size_t)c->n_envs * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return VN_OK;
+}
+
+int vn_nav_progress(vn_ctx* c, int on) {
+  if (!c) return fail(VN_EINVAL, "vn_nav_progress: NULL ctx");
+  if (!c->nav) return fail(VN_ESTATE, "vn_nav_progress: navigation info is not enabled (vn_nav_enable)");
+  DeviceGuard guard(c->device);
+  VN_HIP(hipDeviceSynchronize());
+  shape_destroy(c->shape);
+  c->shape = nullptr;
+  if (!on) return VN_OK;
+  ShapeState* sh = nullptr;
+  int rc = shape_create(&sh, c->n_envs);
+  if (rc != VN_OK) return rc;
+  // every env's record from its current state: a running episode is measured from here
+  rc = shape_launch(sh, c->nav, SHAPE_FORM_REFRESH, c->recs, nullptr, nullptr, nullptr, nullptr, 0);
+  if (rc == VN_OK) {
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) rc = hip_fail(e, "vn_nav_progress: enable");
+  }
+  if (rc != VN_OK) {
+    shape_destroy(sh);
+    return rc;
+  }
+  c->shape = sh;
+  return VN_OK;
+}
+
+int vn_set_nav_progress_outputs(vn_ctx* c, int32_t* dist_before, int32_t* dist_after, int32_t* progress) {
+  if (!c) return fail(VN_EINVAL, "vn_set_nav_progress_outputs: NULL ctx");
+  if (!c->shape) return fail(VN_ESTATE, "vn_set_nav_progress_outputs: progress is not enabled (vn_nav_progress)");
+  c->shape->dist_before = dist_before;
+  c->shape->dist_after = dist_after;
+  c->shape->progress = progress;
+  return VN_OK;
+}
+
+int vn_get_nav_progress_state(vn_ctx* c, int32_t* dst, vn_stream_t stream) {
+  if (!c || !dst) return fail(VN_EINVAL, "vn_get_nav_progress_state: NULL argument");
+  if (!c->shape) return fail(VN_ESTATE, "vn_get_nav_progress_state: progress is not enabled (vn_nav_progress)");
+  DeviceGuard guard(c->device);
+  VN_HIP(hipMemcpyAsync(dst, c->shape->rec, (size_t)c->n_envs * 12, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return VN_OK;
+}
+
+int vn_set_nav_progress_state(vn_ctx* c, const int32_t* src, vn_stream_t stream) {
+  if (!c || !src) return fail(VN_EINVAL, "vn_set_nav_progress_state: NULL argument");
+  if (!c->shape) return fail(VN_ESTATE, "vn_set_nav_progress_state: progress is not enabled (vn_nav_progress)");
+  DeviceGuard guard(c->device);
+  VN_HIP(hipMemcpyAsync(c->shape->rec, src, (size_t)c->n_envs * 12, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return VN_OK;
 }
 
@@ -2008,7 +2074,7 @@ int vn_set_state(vn_ctx* c, const int32_t* src, vn_stream_t stream) {
   hipLaunchKernelGGL(set_state_kernel, dim3((c->n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, c->recs,
                      c->n_envs, src, c->scenes, c->n_scenes, c->graph);
   VN_HIP(hipGetLastError());
-  return cur_refresh(c, VN_OK, (hipStream_t)stream);
+  return cur_refresh(c, shape_refresh(c, VN_OK, nullptr, (hipStream_t)stream), (hipStream_t)stream);
 }
 
 int vn_get_episode_returns(vn_ctx* c, float* dst, vn_stream_t stream) {

@@ -176,6 +176,10 @@ SIGNATURES = {
     "vn_get_nav_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vn_set_nav_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vn_nav_episode_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vn_nav_progress": (c_int, [c_void_p, c_int]),
+    "vn_set_nav_progress_outputs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vn_get_nav_progress_state": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vn_set_nav_progress_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vn_nav_sample_episodes": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_uint32, c_void_p, c_void_p,
                                        P(c_int64), c_void_p]),
     "vn_nav_set_episode_log": (c_int, [c_void_p, P(EpisodeLog)]),
@@ -245,6 +249,8 @@ SIGNATURES.update({
                                         c_void_p]),
     "vn_a2c_returns": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int,
                                       c_int, c_float, c_void_p, c_void_p]),
+    "vn_a2c_returns_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
+                                  c_float, c_float, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "vn_a2c_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int,
                                         c_float, c_float, c_void_p, c_void_p,
                                         c_void_p]),

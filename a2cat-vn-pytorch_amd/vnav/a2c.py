@@ -68,7 +68,8 @@ class A2CTrainer:
                  capture_collectives=False, allreduce_buckets=1, time_collectives=False, dedup_goals=None,
                  unreal=False, pc_weight=0.05, rp_weight=1.0, vr_weight=1.0, pc_gamma=0.9, unreal_envs=16,
                  unreal_source="rollout", nav_metrics=False, expert_weight=None, expert_anneal_steps=0,
-                 pg_coefficient=1.0, geo_curriculum=None):
+                 pg_coefficient=1.0, geo_curriculum=None, shaping_weight=None, shaping_gamma=1.0,
+                 shaping_anneal_steps=0, gae_lambda=1.0):
         self.env = env
         self.lib = _lib.load()
         # check before every replayed UNREAL pass that the side stream's buffers and gradient
@@ -160,6 +161,33 @@ class A2CTrainer:
             self.expert_mask = torch.zeros((T, E), dtype=torch.uint8, **kw)
             self.expert_stats = torch.zeros(4, dtype=torch.float32, **kw)
             self.expert_steps = torch.zeros(1, dtype=torch.int64, **kw)
+        # shaping_weight (None = off) and gae_lambda (1 = the n-step return): the returns of the
+        # update come from vn_a2c_returns_ex (DESIGN.md "Reward shaping and GAE"), which adds
+        # w (d_before - shaping_gamma d_after) to every reward, w annealed linearly to 0 over
+        # shaping_anneal_steps env steps (0: constant), and forms the lambda-return. shape_dist
+        # [T, 2, E]: step t's progress launch writes the distances before and after it into slot
+        # t. The env's reward, ep_return and the LSTM's last-reward input stay the environment's
+        # own. shape_stats = [sum of before, sum of after, invalid steps] of the last update;
+        # shape_steps = the env-step count the anneal reads. With None and 1.0 nothing is
+        # allocated and vn_a2c_returns is called as before.
+        self.gae_lambda = float(gae_lambda)
+        if not 0.0 <= self.gae_lambda <= 1.0:
+            raise ValueError("gae_lambda must lie in [0, 1], got %r" % (gae_lambda,))
+        self.shaping = shaping_weight is not None
+        self.returns_ex = self.shaping or self.gae_lambda != 1.0
+        self.shaping_weight = float(shaping_weight) if self.shaping else 0.0
+        self.shaping_gamma = float(shaping_gamma)
+        self.shaping_anneal_steps = int(shaping_anneal_steps) if self.shaping else 0
+        if self.returns_ex:
+            self.shape_stats = torch.zeros(3, dtype=torch.int64, **kw)
+            self.shape_steps = torch.zeros(1, dtype=torch.int64, **kw)
+            self.shape_dist = None
+        if self.shaping:
+            if not env.nav_info:
+                env.set_nav_info(True)
+            if not env.nav_progress:
+                env.set_nav_progress(True)
+            self.shape_dist = torch.zeros((T, 2, E), dtype=torch.int32, **kw)
         # geo_curriculum (None = off): VectorEnv.set_geodesic_curriculum's keyword arguments. Starts
         # are drawn within `level` actions of the goal, and with window > 0 every update ends its
         # rollout with one curriculum_advance(), inside the captured graph too: the level moves on
@@ -384,6 +412,10 @@ class A2CTrainer:
                        dones=torch.zeros((R, T, S), dtype=torch.bool, device=self.device),
                        masks=torch.zeros((R, T + 1, S), **f32), lra=torch.zeros((R, T + 1, S, A1), **f32),
                        hc0=torch.zeros((R, 2, S, 512), **f32))
+        if self.shaping:  # the first S envs' distances before and after every step
+            self.ur["shape_dist"] = torch.zeros((R, T, 2, S), **i32)
+        if self.returns_ex:
+            self.ur_shape_stats = torch.zeros(3, dtype=torch.int64, device=self.device)
         # the slot drawn this update, copied out of the ring by vn_replay_push_draw (fixed
         # addresses: the replayed pass's launches do not depend on which slot was drawn)
         self.ur_cur = {key: torch.zeros_like(v[0]) for key, v in self.ur.items()}
@@ -494,6 +526,22 @@ class A2CTrainer:
             self._model_view = GoalNavPolicy.wrap(self.net, self.params)
         return self._model_view
 
+    def _returns_ex(self, rewards, dones, boot_out, out, dist, T, E, returns, stats):
+        """vn_a2c_returns_ex with this trainer's gamma, lambda and shaping arguments."""
+        P, c_float = _lib.ptr, ctypes.c_float
+        _lib.check(self.lib.vn_a2c_returns_ex(
+            P(rewards), P(dones), P(boot_out), P(out), P(dist), T, E, self.A, c_float(self.gamma),
+            c_float(self.gae_lambda), c_float(self.shaping_weight), c_float(self.shaping_gamma), P(self.shape_steps),
+            ctypes.c_int64(self.shaping_anneal_steps), P(returns), P(stats), self._stream()), "vn_a2c_returns_ex")
+
+    def shaping_weight_at(self, steps):
+        """The annealed shaping weight at an env-step count, as the device forms it: fp64, rounded
+        once to fp32."""
+        w = float(np.float32(self.shaping_weight))
+        if self.shaping_anneal_steps > 0:
+            w = w * max(0.0, 1.0 - float(steps) / float(self.shaping_anneal_steps))
+        return float(np.float32(w))
+
     def _replay_segments(self):
         """The vn_replay_push_draw segments (include/vnav.h vn_replay_seg) of this trainer's
         ring: the frame rows of every sample (drawn into aux_rows for a replayed aux batch) and,
@@ -528,6 +576,8 @@ class A2CTrainer:
             seg(self.lra, E * A1, T, S * A1, u["lra"][0], (T + 1) * S * A1, c["lra"])
             seg(self.boot_lra, S * A1, 1, S * A1, u["lra"][0, T], (T + 1) * S * A1, c["lra"][T])
             seg(self._hc0, E * 512, 2, S * 512, u["hc0"][0], 2 * S * 512, c["hc0"])
+            if self.shaping:
+                seg(self.shape_dist, E, 2 * T, S, u["shape_dist"][0], 2 * T * S, c["shape_dist"])
         return (_lib.ReplaySeg * len(segs))(*segs)
 
     @property
@@ -590,8 +640,12 @@ class A2CTrainer:
         self.unreal_stats.zero_()
         self.ur_dout.zero_()
         rew, don = u["rewards"], u["dones"]
-        _lib.check(lib.vn_a2c_returns(P(rew), P(don), P(self.ur_out[T * S:]), T, S, A, ctypes.c_float(self.gamma),
-                                      P(self.ur_returns), st), "vn_a2c_returns")
+        if self.returns_ex:  # the drawn slot's distances under the current weight; V from ur_out
+            self._returns_ex(rew, don, self.ur_out[T * S:], self.ur_out, u.get("shape_dist"), T, S, self.ur_returns,
+                             self.ur_shape_stats)
+        else:
+            _lib.check(lib.vn_a2c_returns(P(rew), P(don), P(self.ur_out[T * S:]), T, S, A, ctypes.c_float(self.gamma),
+                                          P(self.ur_returns), st), "vn_a2c_returns")
         if self.vr_weight > 0:
             _lib.check(lib.vn_unreal_vr_grad(P(self.ur_out), P(self.ur_returns), T, S, S, A,
                                              ctypes.c_float(self.vr_weight), P(self.ur_dout), P(self.unreal_stats[3:]),
@@ -778,6 +832,8 @@ class A2CTrainer:
             # step count the schedule below computes this update's learning rate from
             self.expert_mask[0].copy_(info["optimal_mask"])
             self.expert_steps.copy_(self.sched[1:2])
+        if self.returns_ex:  # the step count the shaping weight's anneal reads, as the expert's
+            self.shape_steps.copy_(self.sched[1:2])
         _lib.check(lib.vn_a2c_rollout_begin(
             _lib.ptr(self.sched), _lib.ptr(self.lr_dev), ctypes.c_double(self.learning_rate),
             ctypes.c_double(self.max_time_steps), ctypes.c_int64(N * self.world), T, _lib.ptr(info["img_row"]),
@@ -797,10 +853,14 @@ class A2CTrainer:
                 env.set_row_outputs(None, None)
             if self.expert:  # the mask of the state this step leaves: step t + 1's label
                 env.set_nav_mask_output(self.expert_mask[t + 1] if t + 1 < T else None)
+            if self.shaping:  # this step's distances before and after it: slot t
+                env.set_nav_progress_outputs(self.shape_dist[t, 0], self.shape_dist[t, 1])
             # one launch: the categorical draw from out[t] (Philox counter = updates * T + t from
             # the device schedule), the index-only env step, and the next step's recurrent
             # inputs, carries and episode statistics
             env.step_a2c(self._a2c_steps[t], self.rewards[t], self.dones[t], self.states)
+        if self.shaping:  # steps outside a rollout (an evaluation) write the env's own buffers
+            env.set_nav_progress_outputs(None, None)
         _lib.check(lib.vn_a2c_episode_stats(_lib.ptr(self.stats_env), E, _lib.ptr(self.episode_stats), self._stream()),
                    "vn_a2c_episode_stats")
         if self.nav_metrics:
@@ -838,8 +898,12 @@ class A2CTrainer:
                 with torch.cuda.stream(self._side_u):
                     self._unreal_replay_losses(add=False)
                     self._ev_u1.record(self._side_u)
-        _lib.check(lib.vn_a2c_returns(_lib.ptr(self.rewards), _lib.ptr(self.dones), _lib.ptr(self.boot_out), T, E, A,
-                                      ctypes.c_float(self.gamma), _lib.ptr(self.returns), st), "vn_a2c_returns")
+        if self.returns_ex:  # the same launch shape, with the shaping term and the lambda-return
+            self._returns_ex(self.rewards, self.dones, self.boot_out, self.out, self.shape_dist, T, E, self.returns,
+                             self.shape_stats)
+        else:
+            _lib.check(lib.vn_a2c_returns(_lib.ptr(self.rewards), _lib.ptr(self.dones), _lib.ptr(self.boot_out), T, E,
+                                          A, ctypes.c_float(self.gamma), _lib.ptr(self.returns), st), "vn_a2c_returns")
         if self.expert:  # the same launch shape, with the expert term: the update gains no launch
             _lib.check(lib.vn_a2c_loss_grad_expert(
                 _lib.ptr(self.out), _lib.ptr(self.actions), _lib.ptr(self.returns), _lib.ptr(self.expert_mask), N, A,
@@ -1045,6 +1109,9 @@ class A2CTrainer:
                            self.expert_stats[3:]])
         if self.geo_curriculum is not None:  # this rank's mean level over scenes, in the same fetch
             m = torch.cat([m, self.cur_state[0].to(torch.float32).mean().reshape(1)])
+        if self.shaping:  # the two distance sums (exact in fp64 below 2^53), summed over ranks, and the step count
+            d = vdist.reduce_metrics_(self.shape_stats[:2].to(torch.float64), 0, self.group)
+            m = torch.cat([m.to(torch.float64), d, self.shape_steps.to(torch.float64)])
         return m
 
     def _graph_update(self):
@@ -1097,6 +1164,13 @@ class A2CTrainer:
             expert_term = w * nlq / (N * self.world)  # w * expert_loss * valid / N
             k += 4
         cur = {"curriculum_level": vals[k]} if self.geo_curriculum is not None else {}
+        k += 1 if self.geo_curriculum is not None else 0
+        shaping = {}
+        if self.shaping:  # the mean shaping term per env step, formed in fp64 from the exact sums
+            sb, sa, steps = vals[k:k + 3]
+            w = self.shaping_weight_at(steps)
+            shaping = {"shaping_reward": w * (sb - float(np.float32(self.shaping_gamma)) * sa) / (N * self.world),
+                       "shaping_weight": w}
         dt = time.perf_counter() - t0
         return {
             "step": self.total_steps, "updates": self.num_updates,
@@ -1113,6 +1187,7 @@ class A2CTrainer:
             **nav,
             **expert,
             **cur,
+            **shaping,
         }
 
     def run(self, log_every=10, logger=print):
@@ -1287,6 +1362,10 @@ class A2CTrainer:
             saved["carry"] = {k: getattr(self, k).clone() for k in self._RECURRENT_STATE}
         if self.geo_curriculum is not None:
             saved["cur"] = env.curriculum_state().clone()
+        if self.shaping:
+            saved["progress"] = env.get_nav_progress_state().clone()
+        if self.returns_ex:
+            saved["shape_steps"] = self.shape_steps.clone()
         try:
             env.set_env_scenes(env_scenes)
             env.set_max_episode_steps(limit)
@@ -1329,12 +1408,16 @@ class A2CTrainer:
             env.set_nav_state(saved["nav"])
             if "cur" in saved:  # after set_state: it notes the restored envs' scenes
                 env.set_curriculum_state(saved["cur"])
+            if "progress" in saved:  # after set_state, which starts the record from the states
+                env.set_nav_progress_state(saved["progress"])
             env.nav_episode_stats()  # the per-env accumulators of the surplus episodes: dropped
             env.refresh_nav_outputs()
             env.observe(gather=False)
             for k in ("sched", "stats_env", "episode_stats", "nav_stats"):
                 getattr(self, k).copy_(saved[k])
             self.lr_dev.copy_(saved["lr"])
+            if "shape_steps" in saved:
+                self.shape_steps.copy_(saved["shape_steps"])
             if self.recurrent:
                 for k, v in saved["carry"].items():
                     getattr(self, k).copy_(v)
@@ -1353,6 +1436,8 @@ class A2CTrainer:
             sd["env_nav"] = self.env.get_nav_state().cpu()
         if self.geo_curriculum is not None:  # per scene: level and the running window's counters
             sd["env_curriculum"] = self.env.curriculum_state().cpu()
+        if self.shaping:  # scene, goal and distance of the running episodes
+            sd["env_nav_progress"] = self.env.get_nav_progress_state().cpu()
         if self.replay:  # the replay ring and its draw stream resume exactly
             sd["replay_rows"] = self.replay_rows.cpu()
             sd["replay_meta"] = self.replay_meta.cpu()  # next slot, filled, draw counter, drawn slot
@@ -1413,6 +1498,14 @@ class A2CTrainer:
                 self.env.set_geodesic_curriculum(**self.geo_curriculum)
         if self.expert:  # the env's own mask buffer = the restored states' masks (the next rollout's slot 0)
             self.env.refresh_nav_outputs()
+        if self.shaping:
+            if not self.env.nav_progress:  # set_nav_info above switched it off
+                self.env.set_nav_progress(True)
+            if "env_nav_progress" in sd:
+                self.env.set_nav_progress_state(sd["env_nav_progress"])
+            else:  # set_state has started the record from the restored states
+                warnings.warn("checkpoint holds no progress state (saved without shaping_weight): the running "
+                              "episodes' distances start from their current positions")
         self.num_updates = int(sd["num_updates"])
         self.total_steps = int(sd["total_steps"])
         if "sched" in sd:
@@ -1441,7 +1534,9 @@ class A2CTrainer:
         elif tuple(ring.shape) != tuple(self.replay_rows.shape):
             why = "the checkpoint's ring is %s, this trainer's %s" % (tuple(ring.shape), tuple(self.replay_rows.shape))
         elif need_ur and any("ur_" + key not in sd for key in self.ur):
-            why = "the checkpoint has no UNREAL record in its ring (saved without unreal_source='replay')"
+            why = ("the checkpoint's ring holds no shaping distances (saved without shaping_weight)"
+                   if all("ur_" + key in sd for key in self.ur if key != "shape_dist") else
+                   "the checkpoint has no UNREAL record in its ring (saved without unreal_source='replay')")
         if why is not None:
             warnings.warn("replay ring restarts empty: " + why)
             self.replay_rows.zero_()

@@ -37,6 +37,8 @@ ST_FIELDS = ("scene", "state", "goal", "obs_state", "elapsed", "episode", "sched
 # info keys of nav_info=True, in vn_set_nav_buffers' order, with their dtypes
 NAV_KEYS = (("distance_to_goal", torch.int32), ("optimal_action", torch.int32), ("optimal_mask", torch.uint8),
             ("success", torch.bool), ("spl", torch.float32), ("start_distance", torch.int32))
+# info keys of nav_progress=True (set_nav_progress), both int32
+PROGRESS_KEYS = ("distance_before", "progress")
 
 
 def to_float_chw(frames):
@@ -71,7 +73,7 @@ class VectorEnv:
 
     def __init__(self, scenes, num_envs, seed=0, device=None, max_episode_steps=900, tasks=None,
                  env_scenes=None, autoreset=True, aux_observations=False, reuse_outputs=True,
-                 obs_format="u8_hwc", aux_format=None, nav_info=False, image_size=None):
+                 obs_format="u8_hwc", aux_format=None, nav_info=False, image_size=None, nav_progress=False):
         """obs_format: "u8_hwc" (default) returns and takes uint8 [E,H,W,C] frames; "f32_chw"
         returns and takes float32 [E,C,H,W] frames in [0, 1], every value float(u8) / 255 as
         fp32 division (ScaledFloatFrame's), converted in the step's own launch with the same
@@ -85,6 +87,10 @@ class VectorEnv:
         to the goal on the scene's action graph, -1 = unreachable), ``optimal_action`` /
         ``optimal_mask`` (a / all first actions of a shortest path, -1 / 0 if none), and the
         episode's ``success``, ``spl`` and ``start_distance``.
+        nav_progress: with nav_info, every step's info also carries ``distance_before`` (the
+        distance to the goal before the step) and ``progress`` (how many actions closer the step
+        brought the env, 0 where the goal is unreachable; ``set_nav_progress``). ``reward`` stays
+        the environment's own.
         image_size: (height, width) of the frames the env emits, the reference cached env's
         ``image_size`` (cached.py:19,62-64). Every scene whose frames have another size is
         resized on the device before the scene cache is built (``scenes.resize_scene``); None
@@ -144,6 +150,8 @@ class VectorEnv:
                                           self.device.index, ctypes.byref(handle)), "vn_create")
         self._ctx = handle
         self.nav_info = False
+        self.nav_progress = False
+        self._progress_home = (None, None)
         self.episode_log = None
         self.geo_curriculum = None  # set_geodesic_curriculum's configuration while it is on
         # the env -> scene assignment (vn_set_env_scenes; the native default)
@@ -199,6 +207,10 @@ class VectorEnv:
             self.aux_shapes = tuple((c, H, W) if chw else (H, W, c) for c in (dc, sc, sc))
         if nav_info:
             self.set_nav_info(True)
+        if nav_progress:
+            if not nav_info:
+                raise ValueError("nav_progress=True needs nav_info=True")
+            self.set_nav_progress(True)
 
     def _build_aux_arena(self):
         """Depth [rows,H,W,1] and segmentation [rows,H,W,3] uint8 on the device, indexed by
@@ -247,6 +259,7 @@ class VectorEnv:
         for k, _ in NAV_KEYS:
             self._info.pop(k, None)
         self.nav_info = False
+        self._drop_progress()  # vn_nav_enable switches progress off first
         self.episode_log = None  # the log lives in the nav state
         self.geo_curriculum = None  # vn_nav_enable switches the geodesic curriculum off first
         _lib.check(self.lib.vn_nav_enable(self._ctx, 1 if on else 0), "vn_nav_enable")
@@ -328,6 +341,82 @@ class VectorEnv:
         buf = buf.to(device=self.device, dtype=torch.int32).contiguous()
         _lib.check(self.lib.vn_set_nav_state(self._ctx, _lib.ptr(buf), self._stream()), "vn_set_nav_state")
         # the copy is stream-ordered: keep the source alive until it has run
+        buf.record_stream(torch.cuda.current_stream(self.device))
+
+    # -- geodesic progress (DESIGN.md "Reward shaping and GAE") ------------------
+    def _drop_progress(self):
+        self.nav_progress = False
+        self._progress_home = (None, None)
+        for k in PROGRESS_KEYS:
+            self._info.pop(k, None)
+
+    def _need_progress(self):
+        if not self.nav_progress:
+            raise _lib.VnavError("progress is off: VectorEnv(..., nav_info=True, nav_progress=True)")
+
+    def set_nav_progress(self, on, buffers=None):
+        """Enable / disable the per-step geodesic progress (vn_nav_progress; needs nav_info):
+        info gains ``distance_before`` and ``progress``, int32 [E]. Episodes already running are
+        measured from their current state. ``buffers``: the caller's own (distance_before,
+        progress) tensors, either may be None (not written); default the env's own. The step's
+        ``reward``, ``ep_return`` and every other output are unchanged: a shaped reward is formed
+        by the trainer from these distances (A2CTrainer(shaping_weight=...))."""
+        if on:
+            self._need_nav()
+            if buffers is None:
+                buffers = [torch.zeros(self.num_envs, dtype=torch.int32, device=self.device) for _ in PROGRESS_KEYS]
+            buffers = list(buffers)
+            if len(buffers) != len(PROGRESS_KEYS):
+                raise ValueError("progress buffers: one per key of %s" % (PROGRESS_KEYS,))
+            for k, t in zip(PROGRESS_KEYS, buffers):
+                self._check_out(k, t, torch.int32, self.num_envs)
+        elif not self.nav_info:
+            self._drop_progress()
+            return
+        self.config_generation += 1
+        self._drop_progress()
+        _lib.check(self.lib.vn_nav_progress(self._ctx, 1 if on else 0), "vn_nav_progress")
+        if not on:
+            return
+        self.nav_progress = True
+        self._progress_home = tuple(buffers)
+        for k, t in zip(PROGRESS_KEYS, buffers):
+            if t is not None:
+                self._info[k] = t
+        self.set_nav_progress_outputs(None, None, None)
+
+    def set_nav_progress_outputs(self, before, after, progress=None):
+        """Where the next steps write the distance before the step, the distance after it and
+        the progress: int32 [E] device tensors, e.g. a trainer's per-step slots (any None: not
+        written). All three None: back to the buffers set_nav_progress() was given
+        (vn_set_nav_progress_outputs: a pointer swap, no launch, no sync). The caller keeps the
+        tensors alive while steps may write them."""
+        self._need_progress()
+        if before is None and after is None and progress is None:
+            before, progress = self._progress_home
+        for k, t in (("distance_before", before), ("distance_after", after), ("progress", progress)):
+            self._check_out(k, t, torch.int32, self.num_envs)
+        _lib.check(self.lib.vn_set_nav_progress_outputs(self._ctx, _lib.ptr(before), _lib.ptr(after),
+                                                        _lib.ptr(progress)), "vn_set_nav_progress_outputs")
+
+    def get_nav_progress_state(self):
+        """The progress record a checkpoint needs: int32 [3, E] (scene, goal, distance)."""
+        self._need_progress()
+        buf = torch.empty((3, self.num_envs), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.vn_get_nav_progress_state(self._ctx, _lib.ptr(buf), self._stream()),
+                   "vn_get_nav_progress_state")
+        return buf
+
+    def set_nav_progress_state(self, buf):
+        """Restore get_nav_progress_state()'s table; call it after set_state(), which starts the
+        record again from the states it sets."""
+        self._need_progress()
+        buf = torch.as_tensor(buf)
+        if tuple(buf.shape) != (3, self.num_envs):
+            raise ValueError("progress state must be [3, %d] (this env), got %s" % (self.num_envs, tuple(buf.shape)))
+        buf = buf.to(device=self.device, dtype=torch.int32).contiguous()
+        _lib.check(self.lib.vn_set_nav_progress_state(self._ctx, _lib.ptr(buf), self._stream()),
+                   "vn_set_nav_progress_state")
         buf.record_stream(torch.cuda.current_stream(self.device))
 
     # -- fixed-episode evaluation (DESIGN.md "Fixed-episode evaluation") -------

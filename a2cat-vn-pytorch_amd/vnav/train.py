@@ -125,6 +125,12 @@ class Experiment:
     # the geodesic start curriculum (A2CTrainer geo_curriculum): None = off, else the keyword
     # arguments of VectorEnv.set_geodesic_curriculum (level, mode, window, up, down, step, level_min)
     geo_curriculum = None
+    # geodesic reward shaping and GAE (A2CTrainer shaping_weight / shaping_gamma /
+    # shaping_anneal_steps / gae_lambda): weight None = off, lambda 1 = the n-step return
+    shaping_weight = None
+    shaping_gamma = 1.0
+    shaping_anneal_steps = 0
+    gae_lambda = 1.0
 
     def __init__(self, env_kwargs=None, model_kwargs=None, save_dir=None, seed=0, device=None, logger=print,
                  **overrides):
@@ -164,7 +170,9 @@ class Experiment:
                           cuda_graph=self.cuda_graph and (self.world == 1 or self.capture_collectives),
                           capture_collectives=self.capture_collectives, nav_metrics=self.nav_metrics,
                           expert_weight=self.expert_weight, expert_anneal_steps=self.expert_anneal_steps,
-                          pg_coefficient=self.pg_coefficient, geo_curriculum=self.geo_curriculum)
+                          pg_coefficient=self.pg_coefficient, geo_curriculum=self.geo_curriculum,
+                          shaping_weight=self.shaping_weight, shaping_gamma=self.shaping_gamma,
+                          shaping_anneal_steps=self.shaping_anneal_steps, gae_lambda=self.gae_lambda)
 
     def _setup(self):
         if self.trainer is None:
@@ -524,7 +532,20 @@ def main(argv=None):
     p.add_argument("--cur-min", type=int, default=None, metavar="L", help="the lowest level")
     p.add_argument("--cur-mode", type=int, default=None, choices=(1, 2),
                    help="1: starts only within the level; 2: 0.9 within it, 0.1 farther")
+    p.add_argument("--shaping-weight", type=float, default=None, metavar="W",
+                   help="train on r + W (d_before - G d_after), d the geodesic distance to the goal (the env's "
+                        "own reward and episode returns stay as they are)")
+    p.add_argument("--shaping-gamma", type=float, default=None, metavar="G",
+                   help="the potential's discount G of --shaping-weight (default 1)")
+    p.add_argument("--shaping-anneal", type=int, default=None, metavar="STEPS",
+                   help="anneal the shaping weight linearly to 0 over STEPS env-steps (default: constant)")
+    p.add_argument("--gae-lambda", type=float, default=None, metavar="L",
+                   help="GAE(lambda) advantages and lambda-return critic targets (default 1: n-step returns)")
     a = p.parse_args(argv)
+    if a.shaping_weight is None and (a.shaping_gamma is not None or a.shaping_anneal is not None):
+        p.error("--shaping-gamma / --shaping-anneal need --shaping-weight")
+    if a.gae_lambda is not None and not 0.0 <= a.gae_lambda <= 1.0:
+        p.error("--gae-lambda must lie in [0, 1]")
     cur = dict(window=a.cur_window, up=a.cur_up, down=a.cur_down, step=a.cur_step, level_min=a.cur_min,
                mode=a.cur_mode)
     cur = {k: v for k, v in cur.items() if v is not None}
@@ -560,6 +581,10 @@ def main(argv=None):
         over["expert_anneal_steps"] = a.expert_anneal
     if a.geo_curriculum is not None:
         over["geo_curriculum"] = dict(cur, level=a.geo_curriculum)
+    for key, v in (("shaping_weight", a.shaping_weight), ("shaping_gamma", a.shaping_gamma),
+                   ("shaping_anneal_steps", a.shaping_anneal), ("gae_lambda", a.gae_lambda)):
+        if v is not None:
+            over[key] = v
     exp = make_trainer(a.name, env_kwargs=env_kwargs, save_dir=a.save_dir, seed=a.seed, **over)
     fixed = a.eval_episodes is not None or a.eval_set is not None
     if not fixed and (a.eval_buckets or a.greedy or a.save_eval_set or a.eval_max_steps is not None):

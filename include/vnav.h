@@ -376,6 +376,37 @@ int vn_set_nav_state(vn_ctx* ctx, const int32_t* src_dev_2xE, vn_stream_t stream
  * accumulators are then zeroed. Same inputs, same bits. No host argument: capturable. */
 int vn_nav_episode_stats(vn_ctx* ctx, float* stats4_dev, vn_stream_t stream);
 
+/* Geodesic progress of every step (DESIGN.md "Reward shaping and GAE"): the action-graph
+ * distance to the goal before and after the step, for a dense progress reward formed by the
+ * trainer (vn_a2c_returns_ex). The step's own reward, ep_return and every other output stay as
+ * they are. on = 1 allocates a per-env record [3][n_envs] int32 (scene, goal and distance of the
+ * running episode) and starts it from every env's current state; on = 0 frees it. While it is
+ * on, vn_step / vn_step_f32 / vn_step_aux / vn_step_a2c launch one more small kernel behind the
+ * nav launch (before the curriculum's), one thread per env:
+ *   before = the record's distance;
+ *   after  = 0 where done && !truncated (the state is the goal); geo[goal][terminal_state] of
+ *            the finished episode's scene and goal where done && truncated (after an auto-reset
+ *            the env already holds the next episode, so scene and goal come from the record and
+ *            the state from the step's terminal_state, looked up clamped to the table);
+ *            otherwise the distance of the state the step left the env in;
+ *   progress = before - after where both are >= 0, else 0 (-1: the goal is unreachable);
+ * then the record takes the env's scene, goal and distance (after an auto-reset the new
+ * episode's). vn_reset launches the refresh form for the envs it reset, vn_set_state for every
+ * env. terminal_state is read from the vn_set_info_buffers buffer, or from a stand-in of the
+ * progress state where the caller set none. Synchronises and replaces launch arguments (a
+ * captured graph must be recaptured). VN_ESTATE before vn_nav_enable; vn_nav_enable (either way)
+ * first switches progress off. */
+int vn_nav_progress(vn_ctx* ctx, int on);
+/* Where the following progress launches write, [n_envs] int32 on the device each, any may be
+ * NULL (not written): a host-side pointer swap like vn_set_nav_mask_output, no launch and no
+ * synchronisation (a launch captured in a graph keeps the pointers it was recorded with). The
+ * caller owns the buffers. VN_ESTATE before vn_nav_progress. */
+int vn_set_nav_progress_outputs(vn_ctx* ctx, int32_t* dist_before, int32_t* dist_after, int32_t* progress);
+/* The progress record, [3][n_envs] int32 on the device: scene, goal, distance. Stream-ordered
+ * copies; set after vn_set_state, which refreshes the record from the env states. */
+int vn_get_nav_progress_state(vn_ctx* ctx, int32_t* dst_dev_3xE, vn_stream_t stream);
+int vn_set_nav_progress_state(vn_ctx* ctx, const int32_t* src_dev_3xE, vn_stream_t stream);
+
 /* Fixed-episode evaluation (DESIGN.md "Fixed-episode evaluation").
  * Draws `count` (start, goal) pairs of `scene`, with replacement, uniformly from
  * Q = {(g, s) : dist_lo <= geo[g][s] <= dist_hi}, Q ordered by g, then by s. Exact, so a host
@@ -726,6 +757,29 @@ int vn_policy_sample(const float* out, int n, int num_actions, uint64_t seed, ui
 int vn_policy_greedy(const float* out, int n, int num_actions, int32_t* actions, vn_stream_t stream);
 int vn_a2c_returns(const float* rewards, const uint8_t* dones, const float* bootstrap_out, int T, int E,
                    int num_actions, float gamma, float* returns, vn_stream_t stream);
+/* vn_a2c_returns with geodesic reward shaping and GAE(lambda) (DESIGN.md "Reward shaping and
+ * GAE"), one launch of the same shape. dist [T][2][E] int32: per step the distance before and
+ * after it (vn_set_nav_progress_outputs), may be NULL. out [T*E][8]: the rollout's head outputs,
+ * value in column num_actions; read only when lambda != 1 and may be NULL otherwise.
+ *   w  = weight when anneal_steps <= 0, else weight * max(0, 1 - *steps_dev / anneal_steps) in
+ *        fp64 rounded once to fp32, read on the device by the launch (a captured update anneals);
+ *   F  = w (float(before) - gamma_phi float(after)) where both are >= 0, else 0;
+ *   r' = r + F; where dist == NULL or w == 0 nothing is added and r' is r by bits (-0.0 stays);
+ *   lambda == 1: R_t = r'_t + gamma R_{t+1} (1 - done_t), vn_a2c_returns' expression: with
+ *        dist == NULL or w == 0 the result is vn_a2c_returns' bit for bit;
+ *   lambda != 1: delta_t = r'_t + gamma V_{t+1} (1 - done_t) - V_t (V_T = the bootstrap),
+ *        G_t = delta_t + gamma lambda (1 - done_t) G_{t+1}, G_T = 0, returns_t = G_t + V_t: the
+ *        lambda-return, so vn_a2c_loss_grad*'s returns - V is the GAE advantage.
+ * stats3_dev, int64 on the device, zeroed by the call: with dist, the sums of before and of
+ * after over the steps where both are >= 0 and the number of the other steps (integer atomics:
+ * exact and order-independent); the mean shaping term is w (sum_b - gamma_phi sum_a) / (T E).
+ * VN_EINVAL, nothing written: a NULL rewards / dones / bootstrap_out / returns / stats3_dev,
+ * out NULL with lambda != 1, T <= 0, E <= 0, num_actions outside 1..7, lambda outside [0, 1],
+ * anneal_steps > 0 without steps_dev. */
+int vn_a2c_returns_ex(const float* rewards, const uint8_t* dones, const float* bootstrap_out, const float* out,
+                      const int32_t* dist, int T, int E, int num_actions, float gamma, float lambda, float weight,
+                      float gamma_phi, const int64_t* steps_dev, int64_t anneal_steps, float* returns,
+                      int64_t* stats3_dev, vn_stream_t stream);
 int vn_a2c_loss_grad(const float* out, const int32_t* actions, const float* returns, int n,
                      int num_actions, float value_coef, float entropy_coef, float* dout,
                      float* stats4, vn_stream_t stream);
