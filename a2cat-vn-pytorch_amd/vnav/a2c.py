@@ -45,14 +45,14 @@ csrc/vn_unreal_loss.hip, oracle/unreal.py).
 import ctypes
 import os
 import time
-import warnings
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, checkpoint, evaluation
 from . import dist as vdist
-from .policy import OUT_LD, PolicyNet, frames_from_rows
+from .metrics import metric_layout
+from .policy import OUT_LD, AuxTargets, PolicyNet, frames_from_rows
 
 
 # rows at or below which vn_policy_heads takes its skinny path (kSkinnyRows, csrc/vn_skinny.h):
@@ -202,6 +202,8 @@ class A2CTrainer:
         # update's counter base] and the learning rate of the update (vn_a2c_schedule)
         self.sched = torch.zeros(3, dtype=torch.int64, **kw)
         self.lr_dev = torch.zeros(1, dtype=torch.float32, **kw)
+        self._metric_layout = metric_layout(bool(unreal), self.nav_metrics, self.expert, self.geo_curriculum is not None,
+                                            self.shaping)  # step()'s metric vector: {segment: (offset, width)}
         self.workspace = torch.empty(self.net.workspace_floats(N), dtype=torch.float32, **kw)
         if self.recurrent:
             X = self.net.lstm["xcat"]
@@ -235,7 +237,6 @@ class A2CTrainer:
             self.dx4 = torch.zeros((N, self.net.fc_in), dtype=torch.float32, **kw)
             self.aux_stats = torch.zeros(4, dtype=torch.float32, **kw)
             self.aux_ws = torch.empty(self.net.aux_workspace_floats(), dtype=torch.float32, **kw)
-            from .policy import AuxTargets
             self.aux_table = self.net.aux_target_table(*env.aux_arena)  # once per scene cache
             self._aux_targets = AuxTargets(self.aux_table.data_ptr(), self.rows_img.data_ptr(),
                                            self.rows_goal.data_ptr())
@@ -268,7 +269,6 @@ class A2CTrainer:
             self.aux_out = torch.zeros((N, OUT_LD), dtype=torch.float32, **kw)
             self.aux_dz5 = torch.zeros((N, 512), dtype=torch.float32, **kw)
             self.aux_grads = torch.zeros(P, dtype=torch.float32, **kw)
-            from .policy import AuxTargets
             self._aux_targets_replay = AuxTargets(self.aux_table.data_ptr(), self.aux_rows[0].data_ptr(),
                                                   self.aux_rows[1].data_ptr())
         # compute_auxiliary_loss overridden by a subclass: called every update (autograd on a
@@ -421,11 +421,9 @@ class A2CTrainer:
         self.ur_cur = {key: torch.zeros_like(v[0]) for key, v in self.ur.items()}
         X = net.lstm["xcat"]
         # Side-stream-owned (update(): the replayed pass runs on self._side_u beside the A2C
-        # backward): ur_* and ur_cur, h_pc / pcb / pc_a1 / pc_p2 / dh_pc / pc_ws, rp_x / rp_dx /
-        # rp_out / rp_dout, unreal_stats, and the pc / rp blocks of self.grads
-        # (_side_grad_ranges()). Nothing on the main stream may touch them between the fork and
-        # the join — checked by _check_side_stream_disjoint (VN_DEBUG_STREAMS=1 or
-        # A2CTrainer.debug_streams) and tests/test_unreal_gpu.py.
+        # backward): the buffers _side_owned() lists. Nothing on the main stream may touch them
+        # between the fork and the join — checked by _check_side_stream_disjoint
+        # (VN_DEBUG_STREAMS=1 or A2CTrainer.debug_streams) and tests/test_unreal_gpu.py.
         self.ur_acts = net.new_acts(n)
         self.ur_xcat = torch.zeros((n, X), **f32)
         self.ur_lacts = torch.zeros((n, 2048), **f32)
@@ -448,45 +446,39 @@ class A2CTrainer:
         self._side_u = torch.cuda.Stream(device=self.device)
         self._ev_u0, self._ev_u1 = torch.cuda.Event(), torch.cuda.Event()
 
-    def _unreal_forward_losses(self):
-        """UNREAL losses of this rollout: vr into dout, pc and rp head gradients into grads;
-        returns (dh_extra [T, S, 512], dX4 target). Runs after vn_a2c_loss_grad."""
-        lib, net = self.lib, self.net
-        E, T, A, S = self.env.num_envs, self.num_steps, self.A, self.unreal_S
-        N = T * E
-        P, st = _lib.ptr, self._stream()
+    def _unreal_head_losses(self, net, out, returns, dout, h, x4, actions, rewards, dones, rows_img, rows_last, T, E, S,
+                            dx4, accumulate, h_src=(None, None)):
+        """The UNREAL head losses on the first S of E envs' sequences, on the handle ``net``: value
+        replay of ``out`` into ``dout``; pixel control on ``h`` (rows t*S + e, the bootstrap's at
+        t = T), dL/dh into dh_pc; reward prediction on three consecutive conv_base maps of ``x4``,
+        dL/dX4 into ``dx4`` (added when ``accumulate``); both heads' gradients into grads.
+        ``h_src``: (steps' h, bootstrap's h) of all E envs, gathered into ``h`` by the launch that
+        gathers the rp input (NULL: ``h`` holds them already)."""
+        lib, A, F, P, st = self.lib, self.A, net.fc_in, _lib.ptr, self._stream()
         self.unreal_stats.zero_()
         if self.vr_weight > 0:
-            _lib.check(lib.vn_unreal_vr_grad(P(self.out), P(self.returns), T, E, S, A, ctypes.c_float(self.vr_weight),
-                                             P(self.dout), P(self.unreal_stats[3:]), st), "vn_unreal_vr_grad")
-        # pixel control on h of the first S envs (+ the bootstrap's), reward prediction on three
-        # consecutive conv_base maps of the same envs: both inputs gathered in one launch
-        F = net.fc_in
-        x4 = net.x4(self.acts, N)
-        _lib.check(lib.vn_unreal_gather(P(self.h_all), P(self.boot_h), P(x4), T, E, S, F, P(self.h_pc), P(self.rp_x),
-                                        st), "vn_unreal_gather")
+            _lib.check(lib.vn_unreal_vr_grad(P(out), P(returns), T, E, S, A, ctypes.c_float(self.vr_weight), P(dout),
+                                             P(self.unreal_stats[3:]), st), "vn_unreal_vr_grad")
+        _lib.check(lib.vn_unreal_gather(P(h_src[0]), P(h_src[1]), P(x4), T, E, S, F,
+                                        None if h_src[0] is None else P(h), P(self.rp_x), st), "vn_unreal_gather")
         n_pc = (T + 1) * S
-        net.pc_forward(self.params, self.h_pc, n_pc, self.pcb, self.pc_a1, self.pc_p2, None, self.pc_ws)
+        net.pc_forward(self.params, h, n_pc, self.pcb, self.pc_a1, self.pc_p2, None, self.pc_ws)
         H, W = self.env.frame_shape[:2]
-        info = self.env._info
         # q formed from p2 in the loss kernel, which leaves dL/dp2 in p2 for the backward
-        _lib.check(lib.vn_unreal_pc_loss_grad_ex(P(self.pc_p2), self.pc_cells, P(self.actions), P(self.dones),
+        _lib.check(lib.vn_unreal_pc_loss_grad_ex(P(self.pc_p2), self.pc_cells, P(actions), P(dones),
                                                  ctypes.c_void_p(self._arena), ctypes.c_int64(self._fb), H, W,
-                                                 P(self.rows_img), P(info["img_row"]), T, E, S, A,
-                                                 ctypes.c_float(self.pc_gamma), ctypes.c_float(self.pc_weight),
-                                                 P(self.unreal_stats), st), "vn_unreal_pc_loss_grad")
-        net.pc_backward(self.params, self.h_pc, n_pc, self.pcb, self.pc_a1, self.pc_p2, None, self.grads, self.dh_pc,
-                        self.pc_ws)
+                                                 P(rows_img), P(rows_last), T, E, S, A, ctypes.c_float(self.pc_gamma),
+                                                 ctypes.c_float(self.pc_weight), P(self.unreal_stats), st),
+                   "vn_unreal_pc_loss_grad")
+        net.pc_backward(self.params, h, n_pc, self.pcb, self.pc_a1, self.pc_p2, None, self.grads, self.dh_pc, self.pc_ws)
         n_rp = (T - 2) * S
         net.rp_forward(self.params, self.rp_x, n_rp, self.rp_out)
-        _lib.check(lib.vn_unreal_rp_loss_grad(P(self.rp_out), P(self.rewards), P(self.dones), T, E, S,
+        _lib.check(lib.vn_unreal_rp_loss_grad(P(self.rp_out), P(rewards), P(dones), T, E, S,
                                               ctypes.c_float(self.rp_weight), P(self.rp_dout),
                                               P(self.unreal_stats[1:3]), st), "vn_unreal_rp_loss_grad")
         net.rp_backward(self.params, self.rp_x, n_rp, self.rp_dout, self.grads, self.rp_dx, self.pc_ws)
-        dx4 = self.dx4 if self.rp_into_aux else self.unreal_dx4
-        _lib.check(lib.vn_unreal_rp_scatter(P(self.rp_dx), T, E, S, F, P(dx4), int(self.rp_into_aux), st),
+        _lib.check(lib.vn_unreal_rp_scatter(P(self.rp_dx), T, E, S, F, P(dx4), int(accumulate), st),
                    "vn_unreal_rp_scatter")
-        return self.dh_pc[:T * S], dx4
 
     # deep_rl hook names (experiments/thor_cached_auxiliary.py:50-56)
     def create_env(self, kwargs):
@@ -526,13 +518,21 @@ class A2CTrainer:
             self._model_view = GoalNavPolicy.wrap(self.net, self.params)
         return self._model_view
 
-    def _returns_ex(self, rewards, dones, boot_out, out, dist, T, E, returns, stats):
-        """vn_a2c_returns_ex with this trainer's gamma, lambda and shaping arguments."""
-        P, c_float = _lib.ptr, ctypes.c_float
+    def _returns(self, rewards, dones, boot_out, out, T, E, returns, replayed=False):
+        """The returns of T steps of E envs: vn_a2c_returns, or with shaping / GAE on
+        vn_a2c_returns_ex (the same launch shape) with this trainer's gamma, lambda and shaping
+        arguments; ``replayed``: on the drawn slot's distances, under the current weight."""
+        P, c_float, st = _lib.ptr, ctypes.c_float, self._stream()
+        if not self.returns_ex:
+            _lib.check(self.lib.vn_a2c_returns(P(rewards), P(dones), P(boot_out), T, E, self.A, c_float(self.gamma),
+                                               P(returns), st), "vn_a2c_returns")
+            return
+        dist = self.ur_cur.get("shape_dist") if replayed else self.shape_dist
+        stats = self.ur_shape_stats if replayed else self.shape_stats
         _lib.check(self.lib.vn_a2c_returns_ex(
             P(rewards), P(dones), P(boot_out), P(out), P(dist), T, E, self.A, c_float(self.gamma),
             c_float(self.gae_lambda), c_float(self.shaping_weight), c_float(self.shaping_gamma), P(self.shape_steps),
-            ctypes.c_int64(self.shaping_anneal_steps), P(returns), P(stats), self._stream()), "vn_a2c_returns_ex")
+            ctypes.c_int64(self.shaping_anneal_steps), P(returns), P(stats), st), "vn_a2c_returns_ex")
 
     def shaping_weight_at(self, steps):
         """The annealed shaping weight at an env-step count, as the device forms it: fp64, rounded
@@ -585,10 +585,6 @@ class A2CTrainer:
         """Filled slots of the replay ring (reads the device meta: synchronises)."""
         return int(self.replay_meta[1])
 
-    @property
-    def replay_pos(self):
-        return int(self.replay_meta[0])
-
     def _replay_push_and_sample(self):
         """Store this rollout's frame rows (and, for the UNREAL losses, the first S envs'
         sequences) in the replay ring and draw one stored rollout (uniform over the filled
@@ -602,21 +598,19 @@ class A2CTrainer:
             return None
         return RolloutBatch(self, self.aux_rows[0], self.aux_rows[1])
 
-    def _unreal_replay_losses(self, add=True):
+    def _unreal_replay_losses(self):
         """UnrealTrainer's losses on the first S envs of the stored rollout drawn this update
         (deep_rl samples its sequences from a replay buffer, experiments/ai2_auxiliary/trainer.py
         :21-31; its sequence shape and initial state are absent, parity unpinned): trunk forward
         of their T + 1 observations, the LSTM over T + 1 steps from the (h, c) the rollout started
         from, the heads; value replay against their n-step returns (bootstrapped from step T),
         pixel control on their h, reward prediction on their conv_base maps; then the LSTM and
-        trunk backward of those losses. Adds the trunk / heads / LSTM gradients to grads (the
-        pixel-control and reward-prediction blocks are written there directly); add=False leaves
-        that sum to the caller (update(): after the side stream's join). Runs on the second
-        policy handle (its own split-K scratch)."""
-        lib, net = self.lib, self._net_u
-        T, S, A = self.num_steps, self.unreal_S, self.A
+        trunk backward of those losses: the pixel-control and reward-prediction blocks straight
+        into grads, the trunk / heads / LSTM gradients into ur_grads, which update() adds after
+        the side stream's join. Runs on the second policy handle (its own split-K scratch)."""
+        net = self._net_u
+        T, S = self.num_steps, self.unreal_S
         n = (T + 1) * S
-        P, st = _lib.ptr, self._stream()
         u = self.ur_cur  # the slot vn_replay_push_draw drew this update
         rows = u["rows"]
         frames = self._frames(rows[0], rows[1])
@@ -637,47 +631,20 @@ class A2CTrainer:
             net.lstm_step(self.params, S, x5[sl], u["lra"][t], u["masks"][t], hp, cp, self.ur_xcat[sl],
                           self.ur_gates, self.ur_lacts[sl], c_r[sl], h_r[sl])
         net.heads(self.params, h_r, n, self.ur_out)
-        self.unreal_stats.zero_()
         self.ur_dout.zero_()
         rew, don = u["rewards"], u["dones"]
-        if self.returns_ex:  # the drawn slot's distances under the current weight; V from ur_out
-            self._returns_ex(rew, don, self.ur_out[T * S:], self.ur_out, u.get("shape_dist"), T, S, self.ur_returns,
-                             self.ur_shape_stats)
-        else:
-            _lib.check(lib.vn_a2c_returns(P(rew), P(don), P(self.ur_out[T * S:]), T, S, A, ctypes.c_float(self.gamma),
-                                          P(self.ur_returns), st), "vn_a2c_returns")
-        if self.vr_weight > 0:
-            _lib.check(lib.vn_unreal_vr_grad(P(self.ur_out), P(self.ur_returns), T, S, S, A,
-                                             ctypes.c_float(self.vr_weight), P(self.ur_dout), P(self.unreal_stats[3:]),
-                                             st), "vn_unreal_vr_grad")
-        # pixel control on the replayed h (rows t*S + e, the bootstrap at t = T)
-        net.pc_forward(self.params, h_r, n, self.pcb, self.pc_a1, self.pc_p2, None, self.pc_ws)
-        H, W = self.env.frame_shape[:2]
-        _lib.check(lib.vn_unreal_pc_loss_grad_ex(P(self.pc_p2), self.pc_cells, P(u["actions"]), P(don),
-                                                 ctypes.c_void_p(self._arena), ctypes.c_int64(self._fb), H, W, P(rows[0]),
-                                                 P(rows[0][T * S:]), T, S, S, A, ctypes.c_float(self.pc_gamma),
-                                                 ctypes.c_float(self.pc_weight), P(self.unreal_stats), st),
-                   "vn_unreal_pc_loss_grad")
-        net.pc_backward(self.params, h_r, n, self.pcb, self.pc_a1, self.pc_p2, None, self.grads, self.dh_pc, self.pc_ws)
-        # reward prediction on three consecutive conv_base maps of the replayed envs
-        F = net.fc_in
-        _lib.check(lib.vn_unreal_gather(None, None, P(net.x4(self.ur_acts, n)), T, S, S, F, None, P(self.rp_x), st),
-                   "vn_unreal_gather")
-        n_rp = (T - 2) * S
-        net.rp_forward(self.params, self.rp_x, n_rp, self.rp_out)
-        _lib.check(lib.vn_unreal_rp_loss_grad(P(self.rp_out), P(rew), P(don), T, S, S, ctypes.c_float(self.rp_weight),
-                                              P(self.rp_dout), P(self.unreal_stats[1:3]), st), "vn_unreal_rp_loss_grad")
-        net.rp_backward(self.params, self.rp_x, n_rp, self.rp_dout, self.grads, self.rp_dx, self.pc_ws)
-        _lib.check(lib.vn_unreal_rp_scatter(P(self.rp_dx), T, S, S, F, P(self.ur_dx4), 1 if self._merged_replay else 0,
-                                            st), "vn_unreal_rp_scatter")
+        # the drawn slot's returns (V and the bootstrap from ur_out), then the heads' losses on
+        # the replayed h (rows t*S + e, the bootstrap at t = T) and conv_base maps
+        self._returns(rew, don, self.ur_out[T * S:], self.ur_out, T, S, self.ur_returns, replayed=True)
+        self._unreal_head_losses(net, self.ur_out, self.ur_returns, self.ur_dout, h_r, net.x4(self.ur_acts, n),
+                                 u["actions"], rew, don, rows[0], rows[0][T * S:], T, S, S, self.ur_dx4,
+                                 self._merged_replay)
         # BPTT over the T + 1 replayed steps (value replay's dout + pixel control's dh), the trunk
         net.lstm_backward(self.params, T + 1, S, self.ur_dout, h_r, self.ur_xcat, self.ur_lacts, c_r, c0,
                           u["masks"], x5, self.ur_dz5, self.ur_grads, self.ur_lstm_ws, dh_extra=self.dh_pc,
                           extra_envs=S)
         net.backward_ex(self.params, frames, n, self.ur_acts, n, None, self.ur_dz5, self.ur_dx4, self.ur_grads,
                         self.ur_ws)
-        if add:
-            self.grads[:self._ur_add_end].add_(self.ur_grads[:self._ur_add_end])
 
     def _side_grad_range(self):
         """[lo, hi) of the flat gradient the replayed UNREAL pass writes on the side stream: the
@@ -817,15 +784,32 @@ class A2CTrainer:
                       self.c_all[last], self.boot_xcat, self.gates, self.boot_la, self.boot_c, self.boot_h)
         net.heads(self.params, self.boot_h, E, self.boot_out)
 
+    def _rollout_begin(self):
+        """One launch: the device schedule, step 0's frame rows (later steps' rows are written
+        into their slots by the env step before them) and, recurrent, step 0's mask and
+        [one_hot(a) | r] * m from the carried last action / reward / mask."""
+        E, T, P, info, rec = self.env.num_envs, self.num_steps, _lib.ptr, self.env._info, self.recurrent
+        _lib.check(self.lib.vn_a2c_rollout_begin(
+            P(self.sched), P(self.lr_dev), ctypes.c_double(self.learning_rate), ctypes.c_double(self.max_time_steps),
+            ctypes.c_int64(T * E * self.world), T, P(info["img_row"]), P(info["goal_row"]), P(self.rows_img),
+            P(self.rows_goal), E, P(self.prev_action) if rec else None, P(self.prev_reward) if rec else None,
+            P(self.prev_mask) if rec else None, self.A, P(self.masks) if rec else None, P(self.lra) if rec else None,
+            self._stream()), "vn_a2c_rollout_begin")
+
+    def _redirect_rows(self, t):
+        """The arena rows of the frames step t emits go straight into step t + 1's slots (the last
+        step's into the env's own info rows: the bootstrap and the next rollout read them there)."""
+        E = self.env.num_envs
+        if t + 1 < self.num_steps:
+            nxt = slice((t + 1) * E, (t + 2) * E)
+            self.env.set_row_outputs(self.rows_img[nxt], self.rows_goal[nxt])
+        else:
+            self.env.set_row_outputs(None, None)
+
     def rollout(self):
-        env, net, lib = self.env, self.net, self.lib
-        E, T, A = env.num_envs, self.num_steps, self.A
-        N = T * E
+        env, lib = self.env, self.lib
+        E, T = env.num_envs, self.num_steps
         info = env._info
-        # one launch: the device schedule, step 0's frame rows (later steps' rows are written
-        # into their slots by the env step before them) and, recurrent, step 0's mask and
-        # [one_hot(a) | r] * m from the carried last action / reward / mask
-        rec = self.recurrent
         if self.expert:
             # slot 0 = the mask of the state this rollout starts from (the last step of the one
             # before, a reset or a restored checkpoint left it in the env's own buffer), and the
@@ -834,23 +818,11 @@ class A2CTrainer:
             self.expert_steps.copy_(self.sched[1:2])
         if self.returns_ex:  # the step count the shaping weight's anneal reads, as the expert's
             self.shape_steps.copy_(self.sched[1:2])
-        _lib.check(lib.vn_a2c_rollout_begin(
-            _lib.ptr(self.sched), _lib.ptr(self.lr_dev), ctypes.c_double(self.learning_rate),
-            ctypes.c_double(self.max_time_steps), ctypes.c_int64(N * self.world), T, _lib.ptr(info["img_row"]),
-            _lib.ptr(info["goal_row"]), _lib.ptr(self.rows_img), _lib.ptr(self.rows_goal), E,
-            _lib.ptr(self.prev_action) if rec else None, _lib.ptr(self.prev_reward) if rec else None,
-            _lib.ptr(self.prev_mask) if rec else None, A, _lib.ptr(self.masks) if rec else None,
-            _lib.ptr(self.lra) if rec else None, self._stream()), "vn_a2c_rollout_begin")
+        self._rollout_begin()
         for t in range(T):
             sl = slice(t * E, (t + 1) * E)
             self._policy_step(t, self._frames(self.rows_img[sl], self.rows_goal[sl]))
-            # the emitted frames' arena rows go straight into step t + 1's slots (the last step's
-            # into the env's own info rows: the bootstrap and the next rollout read them there)
-            nxt = slice((t + 1) * E, (t + 2) * E)
-            if t + 1 < T:
-                env.set_row_outputs(self.rows_img[nxt], self.rows_goal[nxt])
-            else:
-                env.set_row_outputs(None, None)
+            self._redirect_rows(t)
             if self.expert:  # the mask of the state this step leaves: step t + 1's label
                 env.set_nav_mask_output(self.expert_mask[t + 1] if t + 1 < T else None)
             if self.shaping:  # this step's distances before and after it: slot t
@@ -890,20 +862,15 @@ class A2CTrainer:
             if self.debug_streams:
                 self._check_side_stream_disjoint()
             if self._unreal_inline:
-                self._unreal_replay_losses(add=False)
+                self._unreal_replay_losses()
             else:
                 main = torch.cuda.current_stream(self.device)
                 self._ev_u0.record(main)
                 self._side_u.wait_event(self._ev_u0)
                 with torch.cuda.stream(self._side_u):
-                    self._unreal_replay_losses(add=False)
+                    self._unreal_replay_losses()
                     self._ev_u1.record(self._side_u)
-        if self.returns_ex:  # the same launch shape, with the shaping term and the lambda-return
-            self._returns_ex(self.rewards, self.dones, self.boot_out, self.out, self.shape_dist, T, E, self.returns,
-                             self.shape_stats)
-        else:
-            _lib.check(lib.vn_a2c_returns(_lib.ptr(self.rewards), _lib.ptr(self.dones), _lib.ptr(self.boot_out), T, E,
-                                          A, ctypes.c_float(self.gamma), _lib.ptr(self.returns), st), "vn_a2c_returns")
+        self._returns(self.rewards, self.dones, self.boot_out, self.out, T, E, self.returns)
         if self.expert:  # the same launch shape, with the expert term: the update gains no launch
             _lib.check(lib.vn_a2c_loss_grad_expert(
                 _lib.ptr(self.out), _lib.ptr(self.actions), _lib.ptr(self.returns), _lib.ptr(self.expert_mask), N, A,
@@ -940,7 +907,12 @@ class A2CTrainer:
             net.aux_backward(self.params, self.acts, N, N, self.a1, self.dpred, self.grads, self.dx4, self.aux_ws)
             dx4 = self.dx4
         if self.unreal and self.unreal_source == "rollout":  # after the aux heads: rp adds to their dX4
-            unreal_dh, dx4 = self._unreal_forward_losses()
+            S = self.unreal_S
+            dx4 = self.dx4 if self.rp_into_aux else self.unreal_dx4
+            self._unreal_head_losses(net, self.out, self.returns, self.dout, self.h_pc, net.x4(self.acts, N),
+                                     self.actions, self.rewards, self.dones, self.rows_img, self.env._info["img_row"],
+                                     T, E, S, dx4, self.rp_into_aux, h_src=(self.h_all, self.boot_h))
+            unreal_dh = self.dh_pc[:T * S]
         frames = self._frames(self.rows_img, self.rows_goal)
         goals = None
         if self.dedup_goals:  # the rollout's goal runs: starts ascending, run lengths
@@ -1029,7 +1001,7 @@ class A2CTrainer:
             self._collect_pending()
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
-        if getattr(self, "_head_work", None) is not None:
+        if self._head_work is not None:
             hw, _ = self.net.offsets["head"]
             scale = vdist.allreduce_gradients_(self.grads[:hw], self.group)
             self._head_work.wait()
@@ -1070,27 +1042,19 @@ class A2CTrainer:
         E, T = self.env.num_envs, self.num_steps
         self._hc0.copy_(self._hc_all.view(2, T, E, 512)[:, T - 1])
 
-    def _add_trunk_grads(self, g):
-        """grads[trunk] += g[trunk]: the conv / conv_merge layers (the only ones backward_ex
-        writes when it is given dZ5 instead of the heads' output gradient)."""
-        w, _ = self.net.offsets["conv1"]
-        _, b = self.net.offsets["fc"]
-        end = b + self.net.shapes["fc"][0]
-        self.grads[w:end].add_(g[w:end])
-
     def _update_metrics(self):
-        """rollout + update; returns the device metric vector [value_loss, action_loss,
-        entropy, return mean, grad norm, aux loss, episodes, return sum, length sum]."""
+        """rollout + update; returns the device metric vector (metrics.metric_layout)."""
         batch, _ = self.sample_training_batch()
         if self.geo_curriculum is not None:  # the rollout's episodes decide the next rollout's level
             self.env.curriculum_advance()
             self.env.curriculum_state(out=self.cur_state)
         self.update(batch)
         N = self.num_steps * self.env.num_envs
-        # [stats / N, grad norm, aux loss (sum of the per-head MSEs, trainer.py:51-54),
-        # episode stats] in one launch; / N is torch's tensor / scalar (times the f32 reciprocal)
-        # with the UNREAL losses + [pc loss, rp loss, vr loss] (means: averaged over ranks too)
-        m = torch.empty(12 if self.unreal else 9, dtype=torch.float32, device=self.device)
+        # the base segment [stats / N, grad norm, aux loss (sum of the per-head MSEs, trainer.py:51-54),
+        # episode stats, the UNREAL losses' means] in one launch; / N is torch's tensor / scalar
+        # (times the f32 reciprocal); the means are averaged over ranks too
+        layout = self._metric_layout
+        m = torch.empty(layout["base"][1], dtype=torch.float32, device=self.device)
         aux = self.aux_weight > 0
         P = _lib.ptr
         _lib.check(self.lib.vn_a2c_metrics_ex(P(self.stats), ctypes.c_float(np.float32(1.0) / np.float32(N)),
@@ -1102,16 +1066,19 @@ class A2CTrainer:
         vdist.reduce_metrics_(m, 6, self.group)
         if self.unreal and self.world > 1:
             m[9:] /= self.world
-        if self.nav_metrics:  # the four nav sums ride behind, summed over ranks
-            m = torch.cat([m, vdist.reduce_metrics_(self.nav_stats.clone(), 0, self.group)])
-        if self.expert:  # then the three expert sums, summed over ranks too, and the weight used
-            m = torch.cat([m, vdist.reduce_metrics_(self.expert_stats[:3].clone(), 0, self.group),
-                           self.expert_stats[3:]])
-        if self.geo_curriculum is not None:  # this rank's mean level over scenes, in the same fetch
-            m = torch.cat([m, self.cur_state[0].to(torch.float32).mean().reshape(1)])
-        if self.shaping:  # the two distance sums (exact in fp64 below 2^53), summed over ranks, and the step count
-            d = vdist.reduce_metrics_(self.shape_stats[:2].to(torch.float64), 0, self.group)
-            m = torch.cat([m.to(torch.float64), d, self.shape_steps.to(torch.float64)])
+        # the segments that ride behind the kernel's in the same fetch, each formed at its turn
+        f64, rsum = torch.float64, lambda t: vdist.reduce_metrics_(t, 0, self.group)  # summed over ranks
+        tails = {
+            "nav": lambda: [rsum(self.nav_stats.clone())],
+            "expert": lambda: [rsum(self.expert_stats[:3].clone()), self.expert_stats[3:]],
+            "curriculum": lambda: [self.cur_state[0].to(torch.float32).mean().reshape(1)],
+            # the sums are exact in fp64 below 2^53: the vector turns fp64 here
+            "shaping": lambda: [rsum(self.shape_stats[:2].to(f64)), self.shape_steps.to(f64)],
+        }
+        for name in list(layout)[1:]:
+            parts = tails[name]()
+            m = torch.cat([m.to(parts[0].dtype)] + parts)
+        assert m.numel() == sum(list(layout.values())[-1])  # the last segment's offset + width
         return m
 
     def _graph_update(self):
@@ -1145,29 +1112,24 @@ class A2CTrainer:
             # a graph replay writes the same static tensor every update: hand out a copy
             return {"raw": m.clone() if self.cuda_graph else m}
         vals = m.tolist()
-        vl, al, ent, ret_mean, gnorm, aux_loss, eps, rsum, lsum = vals[:9]
-        unreal = {}
-        if self.unreal:
-            unreal = {"pc_loss": vals[9], "rp_loss": vals[10], "vr_loss": vals[11]}
+        seg = {name: vals[o:o + w] for name, (o, w) in self._metric_layout.items()}
+        vl, al, ent, ret_mean, gnorm, aux_loss, eps, rsum, lsum = seg["base"][:9]
+        unreal = dict(zip(("pc_loss", "rp_loss", "vr_loss"), seg["base"][9:]))  # empty without the UNREAL losses
         nav = {}
-        k = 12 if self.unreal else 9
         if self.nav_metrics:
-            n_ep, n_ok, spl_sum, _ = vals[k:k + 4]
-            k += 4
+            n_ep, n_ok, spl_sum, _ = seg["nav"]
             nav = {"success_rate": n_ok / n_ep if n_ep else float("nan"),
                    "spl": spl_sum / n_ep if n_ep else float("nan")}
         expert, expert_term = {}, 0.0
         if self.expert:
-            nlq, agree, valid, w = vals[k:k + 4]
+            nlq, agree, valid, w = seg["expert"]
             expert = {"expert_loss": nlq / valid if valid else float("nan"),
                       "expert_agreement": agree / valid if valid else float("nan"), "expert_weight": w}
             expert_term = w * nlq / (N * self.world)  # w * expert_loss * valid / N
-            k += 4
-        cur = {"curriculum_level": vals[k]} if self.geo_curriculum is not None else {}
-        k += 1 if self.geo_curriculum is not None else 0
+        cur = {"curriculum_level": seg["curriculum"][0]} if self.geo_curriculum is not None else {}
         shaping = {}
         if self.shaping:  # the mean shaping term per env step, formed in fp64 from the exact sums
-            sb, sa, steps = vals[k:k + 3]
+            sb, sa, steps = seg["shaping"]
             w = self.shaping_weight_at(steps)
             shaping = {"shaping_reward": w * (sb - float(np.float32(self.shaping_gamma)) * sa) / (N * self.world),
                        "shaping_weight": w}
@@ -1197,363 +1159,18 @@ class A2CTrainer:
                 logger(metrics)
         return self
 
-    def evaluate(self, episodes=10, max_rollouts=10000):
-        """deep_rl's Trainer.test() on this trainer's envs: the current policy (sampled
-        actions), no update, until ``episodes`` episodes have finished on all ranks together
-        (or ``max_rollouts`` rollouts). The recurrent state carries across rollouts as in
-        training; the learning-rate step count is left as it was. Returns the episode count
-        and the mean reward and length of the finished episodes; with ``nav_metrics`` also
-        their success rate, mean SPL and mean start distance (geodesic, in actions); with the
-        expert term on also ``expert_agreement``, the share of the labelled samples whose
-        sampled action starts a shortest path."""
-        saved_sched = self.sched.clone()  # sampling counter and step count: evaluation leaves both
-        # the curriculum's counters see the rollouts below: levels, counters back afterwards
-        saved_cur = self.env.curriculum_state().clone() if self.geo_curriculum is not None else None
-        E, T = self.env.num_envs, self.num_steps
-        tot = torch.zeros(7 if self.nav_metrics else 3, dtype=torch.float64)
-        agree = torch.zeros(2, dtype=torch.float64)  # agreeing, labelled samples
-        for _ in range(int(max_rollouts)):
-            self.rollout()
-            if self.recurrent:  # (h, c) after the last step carry on, as update() does
-                self._carry_states()
-            st = self.episode_stats.to(torch.float64)
-            if self.nav_metrics:
-                st = torch.cat([st, self.nav_stats.to(torch.float64)])
-            vdist.reduce_metrics_(st, 0, self.group)
-            tot += st.cpu()
-            if self.expert:
-                M = self.expert_mask.view(-1).to(torch.int32) & ((1 << self.A) - 1)
-                hit = (M >> self.actions) & 1
-                ag = torch.stack([hit.sum(), (M != 0).sum()]).to(torch.float64)
-                agree += vdist.reduce_metrics_(ag, 0, self.group).cpu()
-            if tot[0] >= episodes:
-                break
-        self.sched.copy_(saved_sched)
-        if saved_cur is not None:
-            self.env.set_curriculum_state(saved_cur)
-        n, rsum, lsum = tot.tolist()[:3]
-        out = {"episodes": n, "reward": rsum / n if n else float("nan"),
-               "episode_length": lsum / n if n else float("nan")}
-        if self.nav_metrics:
-            n_ep, n_ok, spl_sum, start_sum = tot.tolist()[3:]
-            nan = float("nan")
-            out.update(success_rate=n_ok / n_ep if n_ep else nan, spl=spl_sum / n_ep if n_ep else nan,
-                       start_distance=start_sum / n_ep if n_ep else nan)
-        if self.expert:
-            out["expert_agreement"] = float(agree[0] / agree[1]) if agree[1] else float("nan")
-        return out
-
     _RECURRENT_STATE = ("h0", "c0", "prev_action", "prev_reward", "prev_mask")
 
-    # -- fixed-episode evaluation (DESIGN.md "Fixed-episode evaluation") ----------------------
-    def _rollout_greedy(self):
-        """rollout() with the argmax action instead of the sampled one, composed of existing
-        entry points: the forward, explicit heads, vn_policy_greedy, an index-only vn_step and
-        vn_a2c_step_post. No statistics are kept: the evaluation reads the episode log."""
-        env, lib, P = self.env, self.lib, _lib.ptr
-        E, T, A = env.num_envs, self.num_steps, self.A
-        info, rec = env._info, self.recurrent
-        _lib.check(lib.vn_a2c_rollout_begin(
-            P(self.sched), P(self.lr_dev), ctypes.c_double(self.learning_rate),
-            ctypes.c_double(self.max_time_steps), ctypes.c_int64(T * E * self.world), T, P(info["img_row"]),
-            P(info["goal_row"]), P(self.rows_img), P(self.rows_goal), E,
-            P(self.prev_action) if rec else None, P(self.prev_reward) if rec else None,
-            P(self.prev_mask) if rec else None, A, P(self.masks) if rec else None,
-            P(self.lra) if rec else None, self._stream()), "vn_a2c_rollout_begin")
-        scratch = torch.zeros(3, dtype=torch.float32, device=self.device)
-        for t in range(T):
-            sl = slice(t * E, (t + 1) * E)
-            self._policy_step(t, self._frames(self.rows_img[sl], self.rows_goal[sl]))
-            if self._fused_heads:  # the sampled step computes the heads itself
-                self.net.heads(self.params, self.h_all[sl], E, self.out[sl])
-            nxt = slice((t + 1) * E, (t + 2) * E)
-            if t + 1 < T:
-                env.set_row_outputs(self.rows_img[nxt], self.rows_goal[nxt])
-            else:
-                env.set_row_outputs(None, None)
-            _lib.check(lib.vn_policy_greedy(P(self.out[sl]), E, A, P(self.actions[sl]), self._stream()),
-                       "vn_policy_greedy")
-            env.step(self.actions[sl], out=dict(reward=self.rewards[t], done=self.dones[t], state=self.states),
-                     gather=False)
-            _lib.check(lib.vn_a2c_step_post(
-                P(self.actions[sl]), P(self.rewards[t]), P(self.dones[t]), P(info["ep_return"]), P(info["ep_length"]),
-                E, A, P(self.prev_action) if rec else None, P(self.prev_reward) if rec else None,
-                P(self.prev_mask) if rec else None,
-                P(self.lra[t + 1] if t + 1 < T else self.boot_lra) if rec else None,
-                P(self.masks[t + 1] if t + 1 < T else self.boot_mask) if rec else None, P(scratch), self._stream()),
-                "vn_a2c_step_post")
-
-    def evaluate_episodes(self, episode_set, policy="sample", max_episode_steps=None, seed=0):
-        """Run every episode of ``episode_set`` (vnav.EpisodeSet) exactly once with the current
-        policy and leave the trainer and its envs as they were. ``policy``: "sample" (the
-        rollout's categorical draw) or "greedy" (argmax). ``max_episode_steps``: the time limit
-        during the evaluation (default: the env's own; every episode must end, so there must be
-        one). ``seed`` fixes the sampling counters: the same set, parameters and seed give the
-        same results. Needs ``nav_metrics=True``.
-        The episodes are placed statically (episodes.assign_episodes): scenes get envs in
-        proportion to their episode counts, a scene's j-th episode runs on its (j mod m)-th env
-        as that env's (j div m)-th episode, by an exact-replay schedule; the results come from the
-        per-episode log alone, so episodes an env runs after its list are never counted. At world
-        > 1 rank r runs the episodes j = r (mod world); the sums are reduced over ranks, the
-        per-episode arrays are this rank's (``index`` holds their positions in the set).
-        Returns a dict: ``episodes``, ``success_rate``, ``spl``, ``episode_length``, ``reward``,
-        ``start_distance`` over all episodes, ``buckets`` (a list of the same per distance
-        bucket, with ``bucket`` = (lo, hi)), and ``per_episode`` (arrays ``index``, ``success``,
-        ``length``, ``spl``, ``start_distance``, ``reward``)."""
-        from . import episodes as vep
-        env = self.env
-        if not self.nav_metrics:
-            raise ValueError("evaluate_episodes needs A2CTrainer(nav_metrics=True)")
-        if policy not in ("sample", "greedy"):
-            raise ValueError('policy must be "sample" or "greedy", got %r' % (policy,))
-        limit = int(env.max_episode_steps if max_episode_steps is None else max_episode_steps)
-        if limit <= 0:
-            raise ValueError("evaluate_episodes needs a time limit > 0: every episode must end")
-        if len(episode_set) == 0:
-            raise ValueError("the episode set is empty")
-        episode_set.validate(env)
-        index = vep.world_slice(len(episode_set), self.rank, self.world)
-        per = {k: np.zeros(0, dtype=dt) for k, dt in (("success", bool), ("length", np.int32), ("spl", np.float32),
-                                                      ("start_distance", np.int32), ("reward", np.float32))}
-        if len(index):
-            per = self._run_episodes(episode_set.subset(index), policy, limit, int(seed))
-        per["index"] = index
-        # sums per bucket (the last row: all episodes), reduced over ranks in fp64
-        nb = len(episode_set.buckets)
-        bucket = episode_set.bucket[index]
-        sums = np.zeros((nb + 1, 6), dtype=np.float64)
-        for b in range(nb + 1):
-            sel = np.ones(len(index), dtype=bool) if b == nb else bucket == b
-            sums[b] = [sel.sum(), per["success"][sel].sum(), per["spl"][sel].astype(np.float64).sum(),
-                       per["length"][sel].sum(), per["reward"][sel].astype(np.float64).sum(),
-                       per["start_distance"][sel].sum()]
-        if self.world > 1:
-            sums = vdist.reduce_metrics_(torch.as_tensor(sums, device=self.device), 0, self.group).cpu().numpy()
-
-        def means(row):
-            n = row[0]
-            d = n if n else float("nan")
-            return {"episodes": int(n), "success_rate": row[1] / d, "spl": row[2] / d, "episode_length": row[3] / d,
-                    "reward": row[4] / d, "start_distance": row[5] / d}
-        out = means(sums[nb])
-        out["buckets"] = [dict(means(sums[b]), bucket=episode_set.buckets[b]) for b in range(nb)]
-        out["per_episode"] = per
-        return out
-
-    def _run_episodes(self, eps, policy, limit, seed):
-        """evaluate_episodes on this rank's episodes: the per-episode arrays in their order."""
-        from . import episodes as vep
-        env = self.env
-        E, T = env.num_envs, self.num_steps
-        env_scenes, ep_env, ep_slot, want, slots = vep.assign_episodes(eps.scene, E, len(env.scenes))
-        # [E, slots, 2] (start, goal): an env's unused slots repeat a valid pair of its scene
-        first = {int(k): int(np.nonzero(eps.scene == k)[0][0]) for k in np.unique(eps.scene)}
-        pad = np.array([first[int(k)] for k in env_scenes])
-        sched = np.stack([eps.start[pad], eps.goal[pad]], axis=1)[:, None, :].repeat(slots, axis=1).astype(np.int32)
-        sched[ep_env, ep_slot, 0], sched[ep_env, ep_slot, 1] = eps.start, eps.goal
-        # what the evaluation changes, saved
-        torch.cuda.synchronize(self.device)
-        saved = dict(schedule=env._schedule, env_scenes=env.env_scenes.copy(), limit=env.max_episode_steps,
-                     state=env.get_state().clone(), returns=env.get_episode_returns().clone(),
-                     nav=env.get_nav_state().clone(), sched=self.sched.clone(), lr=self.lr_dev.clone(),
-                     stats_env=self.stats_env.clone(), episode_stats=self.episode_stats.clone(),
-                     nav_stats=self.nav_stats.clone())
-        if self.recurrent:
-            saved["carry"] = {k: getattr(self, k).clone() for k in self._RECURRENT_STATE}
-        if self.geo_curriculum is not None:
-            saved["cur"] = env.curriculum_state().clone()
-        if self.shaping:
-            saved["progress"] = env.get_nav_progress_state().clone()
-        if self.returns_ex:
-            saved["shape_steps"] = self.shape_steps.clone()
-        try:
-            env.set_env_scenes(env_scenes)
-            env.set_max_episode_steps(limit)
-            env.set_schedule(sched)
-            log = env.set_episode_log(slots, want)
-            _lib.check(self.lib.vn_reset(env._ctx, None, env._stream()), "vn_reset")
-            env.observe(gather=False)
-            # the sampling counter base from the seed; carries and last action / reward / mask zero
-            self.sched.copy_(torch.tensor([(seed & 0xFFFFFFFF) << 20, int(saved["sched"][1]), 0], dtype=torch.int64))
-            if self.recurrent:
-                for k in self._RECURRENT_STATE:
-                    getattr(self, k).zero_()
-            bound = slots * limit + T
-            steps = 0
-            while True:
-                if policy == "greedy":
-                    self._rollout_greedy()
-                else:
-                    self.rollout()
-                if self.recurrent:
-                    self._carry_states()
-                steps += T
-                if int(log.remaining()) == 0:  # one poll per rollout
-                    break
-                if steps >= bound:
-                    raise RuntimeError("evaluate_episodes: %d episodes unfinished after %d steps (bound %d)"
-                                       % (int(log.remaining()), steps, bound))
-            g = (torch.as_tensor(ep_slot, device=self.device), torch.as_tensor(ep_env, device=self.device))
-            per = {"success": log.success[g].cpu().numpy().astype(bool), "length": log.length[g].cpu().numpy(),
-                   "spl": log.spl[g].cpu().numpy(), "start_distance": log.start_distance[g].cpu().numpy(),
-                   "reward": log.ep_return[g].cpu().numpy()}
-        finally:
-            # everything back: configuration first, then the per-env state it would reset
-            env.set_episode_log(None)
-            env.set_schedule(saved["schedule"])
-            env.set_env_scenes(saved["env_scenes"])
-            env.set_max_episode_steps(saved["limit"])
-            env.set_state(saved["state"])
-            env.set_episode_returns(saved["returns"])
-            env.set_nav_state(saved["nav"])
-            if "cur" in saved:  # after set_state: it notes the restored envs' scenes
-                env.set_curriculum_state(saved["cur"])
-            if "progress" in saved:  # after set_state, which starts the record from the states
-                env.set_nav_progress_state(saved["progress"])
-            env.nav_episode_stats()  # the per-env accumulators of the surplus episodes: dropped
-            env.refresh_nav_outputs()
-            env.observe(gather=False)
-            for k in ("sched", "stats_env", "episode_stats", "nav_stats"):
-                getattr(self, k).copy_(saved[k])
-            self.lr_dev.copy_(saved["lr"])
-            if "shape_steps" in saved:
-                self.shape_steps.copy_(saved["shape_steps"])
-            if self.recurrent:
-                for k, v in saved["carry"].items():
-                    getattr(self, k).copy_(v)
-            torch.cuda.synchronize(self.device)
-        return per
-
-    def state_dict(self):
-        sd = {"params": self.params.detach().cpu(), "square_avg": self.square_avg.cpu(),
-              "env_state": self.env.get_state().cpu(), "env_ep_return": self.env.get_episode_returns().cpu(),
-              "num_updates": self.num_updates, "sched": self.sched.cpu(),
-              "total_steps": self.total_steps, "seed": self.seed, "rank": self.rank, "world": self.world}
-        if self.recurrent:
-            for k in self._RECURRENT_STATE:
-                sd[k] = getattr(self, k).cpu()
-        if self.nav_metrics:  # start distance and length offset of the running episodes
-            sd["env_nav"] = self.env.get_nav_state().cpu()
-        if self.geo_curriculum is not None:  # per scene: level and the running window's counters
-            sd["env_curriculum"] = self.env.curriculum_state().cpu()
-        if self.shaping:  # scene, goal and distance of the running episodes
-            sd["env_nav_progress"] = self.env.get_nav_progress_state().cpu()
-        if self.replay:  # the replay ring and its draw stream resume exactly
-            sd["replay_rows"] = self.replay_rows.cpu()
-            sd["replay_meta"] = self.replay_meta.cpu()  # next slot, filled, draw counter, drawn slot
-            if self.unreal_source == "replay":
-                for key, v in self.ur.items():
-                    sd["ur_" + key] = v.cpu()
-        return sd
-
-    def params_state_dict(self):
-        """The world-agnostic part of the state: parameters, RMSprop state and the update /
-        step counters (what a single-process ``test()`` needs after distributed training)."""
-        return {"params": self.params.detach().cpu(), "square_avg": self.square_avg.cpu(),
-                "num_updates": self.num_updates, "total_steps": self.total_steps, "sched": self.sched.cpu(),
-                "seed": self.seed, "world": self.world, "params_only": True}
-
-    def load_params_state_dict(self, sd):
-        """Parameters (and RMSprop state, counters when present) of any world's checkpoint;
-        the env state and recurrent carry of this trainer are left as they are."""
-        if tuple(sd["params"].shape) != tuple(self.params.shape):
-            raise ValueError("checkpoint holds %d parameters, this policy has %d"
-                             % (sd["params"].numel(), self.params.numel()))
-        self.params.copy_(sd["params"].to(self.device))
-        if "square_avg" in sd:
-            self.square_avg.copy_(sd["square_avg"].to(self.device))
-        self.num_updates = int(sd.get("num_updates", self.num_updates))
-        self.total_steps = int(sd.get("total_steps", self.total_steps))
-        if "sched" in sd:
-            self.sched.copy_(sd["sched"].to(self.device))
-
-    def load_state_dict(self, sd):
-        """Restore a state_dict() of this rank (env shard, running returns, recurrent carry
-        are per rank; the env count must match)."""
-        E = self.env.num_envs
-        if tuple(sd["env_ep_return"].shape) != (E,):
-            raise ValueError("checkpoint holds %d envs, this trainer has %d" % (sd["env_ep_return"].shape[0], E))
-        if "world" in sd and (int(sd["world"]), int(sd["rank"])) != (self.world, self.rank):
-            raise ValueError("checkpoint of rank %d/%d loaded on rank %d/%d"
-                             % (int(sd["rank"]), int(sd["world"]), self.rank, self.world))
-        self.params.copy_(sd["params"].to(self.device))
-        self.square_avg.copy_(sd["square_avg"].to(self.device))
-        self.env.set_state(sd["env_state"])
-        self.env.set_episode_returns(sd["env_ep_return"])
-        if self.nav_metrics:
-            if "env_nav" in sd:
-                self.env.set_nav_state(sd["env_nav"])
-            else:
-                warnings.warn("checkpoint holds no navigation state (saved without nav_metrics): the running "
-                              "episodes are measured from their current positions")
-                self.env.set_nav_info(True)
-                if self.geo_curriculum is not None:  # set_nav_info switched it off
-                    self.env.set_geodesic_curriculum(**self.geo_curriculum)
-        if self.geo_curriculum is not None:
-            if "env_curriculum" in sd:
-                self.env.set_curriculum_state(sd["env_curriculum"].to(self.device))
-            else:
-                warnings.warn("checkpoint holds no curriculum state (saved without geo_curriculum): every scene "
-                              "starts from the configured level")
-                self.env.set_geodesic_curriculum(**self.geo_curriculum)
-        if self.expert:  # the env's own mask buffer = the restored states' masks (the next rollout's slot 0)
-            self.env.refresh_nav_outputs()
-        if self.shaping:
-            if not self.env.nav_progress:  # set_nav_info above switched it off
-                self.env.set_nav_progress(True)
-            if "env_nav_progress" in sd:
-                self.env.set_nav_progress_state(sd["env_nav_progress"])
-            else:  # set_state has started the record from the restored states
-                warnings.warn("checkpoint holds no progress state (saved without shaping_weight): the running "
-                              "episodes' distances start from their current positions")
-        self.num_updates = int(sd["num_updates"])
-        self.total_steps = int(sd["total_steps"])
-        if "sched" in sd:
-            self.sched.copy_(sd["sched"].to(self.device))
-        else:  # checkpoints from before the schedule was saved
-            self.sched.copy_(torch.tensor([self.num_updates * self.num_steps, self.total_steps, 0], dtype=torch.int64))
-        if self.recurrent:
-            for k in self._RECURRENT_STATE:
-                getattr(self, k).copy_(sd[k].to(self.device))
-        if self.replay:
-            self._load_replay_state(sd)
-        self.env.observe(gather=False)
-
-    def _load_replay_state(self, sd):
-        """The replay ring of a checkpoint. The ring restarts empty (with a warning) when the
-        checkpoint has no ring, a ring of another capacity, or no UNREAL record while this
-        trainer replays the UNREAL losses (a checkpoint of aux-only replay or of
-        unreal_source='rollout'): restoring the frame rows alone would draw slots whose UNREAL
-        record is empty. Checkpoints from before the device-side ring (host draw stream,
-        'replay_fill_pos') keep their slots; the draw stream restarts at counter 0."""
-        ring = sd.get("replay_rows")
-        need_ur = self.unreal_source == "replay"
-        why = None
-        if ring is None:
-            why = "the checkpoint holds no replay ring"
-        elif tuple(ring.shape) != tuple(self.replay_rows.shape):
-            why = "the checkpoint's ring is %s, this trainer's %s" % (tuple(ring.shape), tuple(self.replay_rows.shape))
-        elif need_ur and any("ur_" + key not in sd for key in self.ur):
-            why = ("the checkpoint's ring holds no shaping distances (saved without shaping_weight)"
-                   if all("ur_" + key in sd for key in self.ur if key != "shape_dist") else
-                   "the checkpoint has no UNREAL record in its ring (saved without unreal_source='replay')")
-        if why is not None:
-            warnings.warn("replay ring restarts empty: " + why)
-            self.replay_rows.zero_()
-            self.replay_meta.zero_()
-            if need_ur:
-                for v in self.ur.values():
-                    v.zero_()
-            return
-        self.replay_rows.copy_(ring.to(self.device))
-        if "replay_meta" in sd:
-            self.replay_meta.copy_(sd["replay_meta"].to(self.device))
-        else:
-            pos_filled = [int(x) for x in sd["replay_fill_pos"]]
-            self.replay_meta.copy_(torch.tensor([pos_filled[1], pos_filled[0], 0, 0], dtype=torch.int64))
-        if need_ur:
-            for key, v in self.ur.items():
-                v.copy_(sd["ur_" + key].to(self.device))
+    # off the update path: the functions of evaluation.py and checkpoint.py, which take the trainer
+    evaluate = evaluation.evaluate
+    evaluate_episodes = evaluation.evaluate_episodes
+    _run_episodes = evaluation._run_episodes
+    _rollout_greedy = evaluation._rollout_greedy
+    state_dict = checkpoint.state_dict
+    params_state_dict = checkpoint.params_state_dict
+    load_params_state_dict = checkpoint.load_params_state_dict
+    load_state_dict = checkpoint.load_state_dict
+    _load_replay_state = checkpoint._load_replay_state
 
 
 class RolloutBatch(dict):

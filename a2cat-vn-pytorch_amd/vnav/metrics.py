@@ -1,0 +1,23 @@
+"""The layout of the metric vector an A2CTrainer update returns (``step(sync=False)["raw"]``), stated
+once: _update_metrics assembles the vector from it, step() decodes it by segment name. Pure Python."""
+
+
+def metric_layout(unreal=False, nav_metrics=False, expert=False, geo_curriculum=False, shaping=False):
+    """{segment: (offset, width)} of the vector under these trainer flags, in the vector's order
+    (its width: the last segment's offset + width). fp64 with ``shaping``, whose distance sums
+    are exact there, fp32 otherwise."""
+    segments = (
+        # value loss, action loss, entropy, return mean, grad norm, aux loss, episodes, return sum,
+        # length sum; with the UNREAL losses + pc loss, rp loss, vr loss (vn_a2c_metrics_ex)
+        ("base", 12 if unreal else 9, True),
+        ("nav", 4, nav_metrics),  # episodes, successes, SPL sum, start-distance sum
+        ("expert", 4, expert),  # sum of -log q, agreeing samples, labelled samples, the weight used
+        ("curriculum", 1, geo_curriculum),  # this rank's mean level over scenes
+        ("shaping", 3, shaping),  # distance-before sum, distance-after sum, the anneal's step count
+    )
+    layout, offset = {}, 0
+    for name, width, on in segments:
+        if on:
+            layout[name] = (offset, width)
+            offset += width
+    return layout

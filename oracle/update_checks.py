@@ -4,7 +4,7 @@ second_update_vs_fp64 runs a trainer's second rollout + update on a small random
 restates it on the CPU: the env transitions on the oracle env driven by the same actions, the
 sampled actions by the Philox inverse-CDF draw on the rollout's logits, the masked trunk, the
 LSTM with the MaskedRNN convention, the heads, the returns, the A2C loss, the aux deconv MSE
-and — with unreal=True — the UNREAL terms as A2CTrainer._unreal_forward_losses wires them:
+and — with unreal=True — the UNREAL terms as A2CTrainer._unreal_head_losses wires them:
   * pixel control (oracle.policy.pixel_control / bighouse_pixel_control, oracle.unreal.pc_loss)
     on h_t of the envs e < S for t < T plus the bootstrap h; the frames of pixel_change are the
     rollout's image rows and, for the observation after the last step, the env's current
