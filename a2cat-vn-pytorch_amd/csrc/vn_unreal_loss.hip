@@ -152,6 +152,34 @@ __global__ __launch_bounds__(256) void unreal_pc_loss_kernel(float* __restrict__
   if (threadIdx.x == 0 && t != 0.0f) atomicAdd(stats, t);
 }
 
+// One reward-prediction sample (both rp loss kernels): g[0..3] = the gradient of the mean
+// cross-entropy w.r.t. its logits l[0..3] for class cls, times weight * inv (0 when unused);
+// returns its cross-entropy.
+__device__ __forceinline__ float rp_sample_loss_grad(const float* __restrict__ l, int cls, bool used, float weight,
+                                                     float inv, float* __restrict__ g) {
+  const float m = fmaxf(l[0], fmaxf(l[1], l[2]));
+  const float ex[3] = {expf(l[0] - m), expf(l[1] - m), expf(l[2] - m)};
+  const float z = ex[0] + ex[1] + ex[2];
+  // p_cls - 1 = -(the other classes' mass) / z: once that mass is below 2^-6 z the difference
+  // is taken in this form. ex[cls] / z - 1 carries the absolute error 2^-24 of rounding the
+  // quotient next to 1, so a trained predictor's class gradient lost its relative precision
+  // (from a margin of about 18 on it was exactly 0 while the other two classes kept theirs). Above
+  // the threshold the difference is within 2^-24 / 2^-6 < 4e-6 of itself and is kept: every
+  // unsaturated sample computes the bits it computed before.
+  float oth = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    if (c != cls) oth += ex[c];
+  const bool sat = oth < 0.015625f * z;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float pd = c == cls ? (sat ? -oth / z : ex[c] / z - 1.0f) : ex[c] / z;
+    g[c] = used ? pd * weight * inv : 0.0f;
+  }
+  g[3] = 0.0f;
+  return logf(z) + m - l[cls];
+}
+
 // Reward prediction, one workgroup: sample j = (ts - 2) S + e (frames ts-2, ts-1, ts of env
 // e, 2 <= ts < T) is used when no episode ends at ts-2 or ts-1; dlogits of the mean
 // cross-entropy over the used samples, times the weight; stats[0] = the mean CE, stats[1] =
@@ -177,29 +205,38 @@ __global__ __launch_bounds__(kRpThreads) void unreal_rp_loss_kernel(const float*
     const bool used = !(dones[(int64_t)(ts - 2) * E + e] || dones[(int64_t)(ts - 1) * E + e]);
     const float r = rewards[(int64_t)ts * E + e];
     const int cls = r == 0.0f ? 0 : (r > 0.0f ? 1 : 2);
-    const float* l = logits + (int64_t)j * 4;
-    const float m = fmaxf(l[0], fmaxf(l[1], l[2]));
-    const float ex[3] = {expf(l[0] - m), expf(l[1] - m), expf(l[2] - m)};
-    const float z = ex[0] + ex[1] + ex[2];
-    float* g = dlogits + (int64_t)j * 4;
-    // p_cls - 1 = -(the other classes' mass) / z: once that mass is below 2^-6 z the difference
-    // is taken in this form. ex[cls] / z - 1 carries the absolute error 2^-24 of rounding the
-    // quotient next to 1, so a trained predictor's class gradient lost its relative precision
-    // (from a margin of about 18 on it was exactly 0 while the other two classes kept theirs). Above
-    // the threshold the difference is within 2^-24 / 2^-6 < 4e-6 of itself and is kept: every
-    // unsaturated sample computes the bits it computed before.
-    float oth = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      if (c != cls) oth += ex[c];
-    const bool sat = oth < 0.015625f * z;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float pd = c == cls ? (sat ? -oth / z : ex[c] / z - 1.0f) : ex[c] / z;
-      g[c] = used ? pd * weight * inv : 0.0f;
-    }
-    g[3] = 0.0f;
-    if (used) ce += logf(z) + m - l[cls];
+    const float v = rp_sample_loss_grad(logits + (int64_t)j * 4, cls, used, weight, inv, dlogits + (int64_t)j * 4);
+    if (used) ce += v;
+  }
+  const float total = block_sum<kRpThreads>(ce, red);
+  if (threadIdx.x == 0) {
+    stats[0] = total * inv;
+    stats[1] = count;
+  }
+}
+
+// The same loss with the class and the used flag given: label[j] = 0 / 1 / 2, anything else
+// (-1 by convention) = unused. The thread mapping and both reductions are the kernel's above, so
+// equal logits under equivalent labels give equal bits.
+__global__ __launch_bounds__(kRpThreads) void unreal_rp_loss_labels_kernel(const float* __restrict__ logits,
+                                                                           const int32_t* __restrict__ label, int n,
+                                                                           float weight, float* __restrict__ dlogits,
+                                                                           float* __restrict__ stats) {
+  __shared__ float red[kRpThreads / 64];
+  float cnt = 0.0f;
+  for (int j = threadIdx.x; j < n; j += kRpThreads) {
+    const int lb = label[j];
+    cnt += (lb >= 0 && lb <= 2) ? 1.0f : 0.0f;
+  }
+  const float count = block_sum<kRpThreads>(cnt, red);
+  const float inv = count > 0.0f ? 1.0f / count : 0.0f;
+  float ce = 0.0f;
+  for (int j = threadIdx.x; j < n; j += kRpThreads) {
+    const int lb = label[j];
+    const bool used = lb >= 0 && lb <= 2;
+    const float v = rp_sample_loss_grad(logits + (int64_t)j * 4, used ? lb : 0, used, weight, inv,
+                                        dlogits + (int64_t)j * 4);
+    if (used) ce += v;
   }
   const float total = block_sum<kRpThreads>(ce, red);
   if (threadIdx.x == 0) {
@@ -307,6 +344,16 @@ int vn_unreal_rp_loss_grad(const float* logits, const float* rewards, const uint
     return fail(VN_EINVAL, "vn_unreal_rp_loss_grad: bad args (needs T >= 3)");
   hipLaunchKernelGGL(unreal_rp_loss_kernel, dim3(1), dim3(kRpThreads), 0, (hipStream_t)stream, logits, rewards, dones,
                      T, E, S, weight, dlogits, stats2);
+  VN_HIP(hipGetLastError());
+  return VN_OK;
+}
+
+int vn_unreal_rp_loss_grad_labels(const float* logits, const int32_t* label, int n, float weight, float* dlogits,
+                                  float* stats2, vn_stream_t stream) {
+  if (!logits || !label || !dlogits || !stats2 || n <= 0)
+    return fail(VN_EINVAL, "vn_unreal_rp_loss_grad_labels: bad args (needs n > 0)");
+  hipLaunchKernelGGL(unreal_rp_loss_labels_kernel, dim3(1), dim3(kRpThreads), 0, (hipStream_t)stream, logits, label, n,
+                     weight, dlogits, stats2);
   VN_HIP(hipGetLastError());
   return VN_OK;
 }

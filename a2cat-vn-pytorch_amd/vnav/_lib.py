@@ -78,6 +78,7 @@ class ObsSet(ctypes.Structure):
 
 
 OBS_U8_HWC, OBS_F32_CHW = 0, 1  # vn_obs_set.format
+RP_SAMPLE_MAX_CANDIDATES = 1 << 20  # VN_RP_SAMPLE_MAX_CANDIDATES: vn_unreal_rp_sample's window limit
 
 
 class GoalRuns(ctypes.Structure):
@@ -103,6 +104,19 @@ class ReplaySeg(ctypes.Structure):
         ("cols", c_int),
         ("elem_bytes", c_int),
         ("pad_", c_int),
+    ]
+
+
+class RpRing(ctypes.Structure):
+    """vn_rp_ring (include/vnav.h)."""
+    _fields_ = [
+        ("rewards", c_void_p),
+        ("dones", c_void_p),
+        ("rows", c_void_p),
+        ("meta4", c_void_p),
+        ("capacity", c_int32),
+        ("T", c_int32),
+        ("S", c_int32),
     ]
 
 
@@ -235,6 +249,9 @@ SIGNATURES.update({
                                           c_void_p]),
     "vn_unreal_rp_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p,
                                        c_void_p, c_void_p]),
+    "vn_unreal_rp_loss_grad_labels": (c_int, [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "vn_unreal_rp_sample": (c_int, [P(RpRing), c_int, c_double, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
     "vn_unreal_rp_scatter": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "vn_unreal_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_void_p]),

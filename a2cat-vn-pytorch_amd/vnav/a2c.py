@@ -69,7 +69,7 @@ class A2CTrainer:
                  unreal=False, pc_weight=0.05, rp_weight=1.0, vr_weight=1.0, pc_gamma=0.9, unreal_envs=16,
                  unreal_source="rollout", nav_metrics=False, expert_weight=None, expert_anneal_steps=0,
                  pg_coefficient=1.0, geo_curriculum=None, shaping_weight=None, shaping_gamma=1.0,
-                 shaping_anneal_steps=0, gae_lambda=1.0):
+                 shaping_anneal_steps=0, gae_lambda=1.0, rp_sampling="sequence", rp_batch=None, rp_skew=0.5):
         self.env = env
         self.lib = _lib.load()
         # check before every replayed UNREAL pass that the side stream's buffers and gradient
@@ -202,8 +202,31 @@ class A2CTrainer:
         # update's counter base] and the learning rate of the update (vn_a2c_schedule)
         self.sched = torch.zeros(3, dtype=torch.int64, **kw)
         self.lr_dev = torch.zeros(1, dtype=torch.float32, **kw)
+        # rp_sampling: where the reward-prediction samples come from. "sequence" = the three-frame
+        # windows of the rollout the other UNREAL losses run on. "skewed" = rp_batch windows drawn
+        # from every filled slot of the replay ring with P(reward != 0) = rp_skew, the published
+        # rule (vn_unreal_rp_sample, DESIGN.md "Reward-skewed reward prediction"): their 3 rp_batch
+        # frames ride behind the replayed pass's own trunk rows. rp_batch None = unreal_envs.
+        if rp_sampling not in ("sequence", "skewed"):
+            raise ValueError("rp_sampling must be 'sequence' or 'skewed'")
+        self.rp_sampling = rp_sampling
+        self.rp_skewed = rp_sampling == "skewed"
+        self.rp_skew = float(rp_skew)
+        self.rp_batch = None if rp_batch is None else int(rp_batch)
+        if self.rp_skewed:
+            if not (unreal and unreal_source == "replay"):
+                raise ValueError("rp_sampling='skewed' draws from the replay ring: it needs unreal=True and "
+                                 "unreal_source='replay'")
+            if os.environ.get("VN_REPLAY_MERGED"):
+                raise ValueError("rp_sampling='skewed' does not run with VN_REPLAY_MERGED=1: the merged pass runs the "
+                                 "aux heads on the replayed pass's activation store, which here also holds the "
+                                 "sampled frames")
+            if not 0.0 <= self.rp_skew <= 1.0:
+                raise ValueError("rp_skew must lie in [0, 1], got %r" % (rp_skew,))
+            if self.rp_batch is not None and self.rp_batch < 1:
+                raise ValueError("rp_batch must be at least 1, got %r" % (rp_batch,))
         self._metric_layout = metric_layout(bool(unreal), self.nav_metrics, self.expert, self.geo_curriculum is not None,
-                                            self.shaping)  # step()'s metric vector: {segment: (offset, width)}
+                                            self.shaping, self.rp_skewed)  # step()'s vector: {segment: (offset, width)}
         self.workspace = torch.empty(self.net.workspace_floats(N), dtype=torch.float32, **kw)
         if self.recurrent:
             X = self.net.lstm["xcat"]
@@ -384,9 +407,12 @@ class A2CTrainer:
         self.dh_pc = torch.zeros((n_pc, 512), **kw)
         self.pc_ws = torch.empty(net.pc_workspace_floats(), **kw)
         F = net.fc_in
-        n_rp = (T - 2) * S
-        self.rp_x = torch.zeros((n_rp, 3 * F), **kw)
-        self.rp_dx = torch.zeros((n_rp, 3 * F), **kw)
+        # reward-prediction samples: every window of the S sequences, or rp_batch drawn ones (then
+        # rp_x / rp_dx are views of the replayed pass's own buffers, _setup_unreal_replay)
+        n_rp = self.rp_n = (self.rp_batch or S) if self.rp_skewed else (T - 2) * S
+        if not self.rp_skewed:
+            self.rp_x = torch.zeros((n_rp, 3 * F), **kw)
+            self.rp_dx = torch.zeros((n_rp, 3 * F), **kw)
         self.rp_out = torch.zeros((n_rp, 4), **kw)
         self.rp_dout = torch.zeros((n_rp, 4), **kw)
         # rp's gradient w.r.t. conv_base's map: into the aux heads' dX4 when those run on the
@@ -419,12 +445,33 @@ class A2CTrainer:
         # the slot drawn this update, copied out of the ring by vn_replay_push_draw (fixed
         # addresses: the replayed pass's launches do not depend on which slot was drawn)
         self.ur_cur = {key: torch.zeros_like(v[0]) for key, v in self.ur.items()}
+        # rp_sampling='skewed': the 3 rp_n sampled frames (sample-major: window j's frames are rows
+        # n + 3 j + m) ride behind the drawn slot's n rows through the same trunk forward and
+        # backward. One row table holds both (the slot's rows drawn into its first n columns, the
+        # sampler's output behind them); conv_base's maps of the appended rows are rp's input as
+        # they lie, and the appended rows of dX4 are its input gradient: no gather, no scatter.
+        cap = self.ur_cap = n + (3 * self.rp_n if self.rp_skewed else 0)
+        if self.rp_skewed:
+            if R * (T - 2) * S > _lib.RP_SAMPLE_MAX_CANDIDATES:
+                raise ValueError("rp_sampling='skewed': replay_size * (num_steps - 2) * unreal_envs = %d windows exceed "
+                                 "the sampler's %d" % (R * (T - 2) * S, _lib.RP_SAMPLE_MAX_CANDIDATES))
+            self.ur_rows_ext = torch.zeros((2, cap), **i32)
+            self.ur_cur["rows"] = self.ur_rows_ext[:, :n]
+            self.rp_rows = self.ur_rows_ext[:, n:].unflatten(1, (self.rp_n, 3))  # [2][rp_n][3] views
+            self.rp_label = torch.zeros(self.rp_n, **i32)
+            self.rp_src = torch.zeros(self.rp_n, **i32)
+            self.rp_draw_stats = torch.zeros(4, **i32)  # |Q0|, |Q1|, draws with a reward, non-void draws
+            u = self.ur
+            self._rp_ring = _lib.RpRing(u["rewards"].data_ptr(), u["dones"].data_ptr(), u["rows"].data_ptr(),
+                                        self.replay_meta.data_ptr(), R, T, S)
+            # the counter is the ring's own draw counter (replay_meta[2]): no state of its own
+            self._rp_seed = vdist.rank_seed(self.seed + 29, self.rank) & ((1 << 64) - 1)
         X = net.lstm["xcat"]
         # Side-stream-owned (update(): the replayed pass runs on self._side_u beside the A2C
         # backward): the buffers _side_owned() lists. Nothing on the main stream may touch them
         # between the fork and the join — checked by _check_side_stream_disjoint
         # (VN_DEBUG_STREAMS=1 or A2CTrainer.debug_streams) and tests/test_unreal_gpu.py.
-        self.ur_acts = net.new_acts(n)
+        self.ur_acts = net.new_acts(cap)
         self.ur_xcat = torch.zeros((n, X), **f32)
         self.ur_lacts = torch.zeros((n, 2048), **f32)
         self.ur_hc = torch.zeros((2, n, 512), **f32)
@@ -432,10 +479,15 @@ class A2CTrainer:
         self.ur_out = torch.zeros((n, OUT_LD), **f32)
         self.ur_returns = torch.zeros(T * S, **f32)
         self.ur_dout = torch.zeros((n, OUT_LD), **f32)
-        self.ur_dz5 = torch.zeros((n, 512), **f32)
-        self.ur_dx4 = torch.zeros((n, net.fc_in), **f32)  # the bootstrap rows stay zero
+        self.ur_dz5 = torch.zeros((cap, 512), **f32)  # the sampled frames' rows stay zero
+        # the bootstrap rows stay zero; skewed: so do the slot's rows, rp writes the appended ones
+        self.ur_dx4 = torch.zeros((cap, net.fc_in), **f32)
         self.ur_grads = torch.zeros(net.n_params, **f32)
-        self.ur_ws = torch.empty(net.workspace_floats(n), **f32)
+        self.ur_ws = torch.empty(net.workspace_floats(cap), **f32)
+        if self.rp_skewed:
+            F = net.fc_in
+            self.rp_x = net.x4(self.ur_acts, cap)[n:].view(self.rp_n, 3 * F)
+            self.rp_dx = self.ur_dx4[n:].view(self.rp_n, 3 * F)
         self.ur_lstm_ws = torch.empty(net.lstm_workspace_floats(T + 1, S), **f32)
         # the grads of the trunk, heads and LSTM (everything before the aux / UNREAL blocks)
         self._ur_add_end = net.lstm["bhh"] + 2048
@@ -459,8 +511,9 @@ class A2CTrainer:
         if self.vr_weight > 0:
             _lib.check(lib.vn_unreal_vr_grad(P(out), P(returns), T, E, S, A, ctypes.c_float(self.vr_weight), P(dout),
                                              P(self.unreal_stats[3:]), st), "vn_unreal_vr_grad")
-        _lib.check(lib.vn_unreal_gather(P(h_src[0]), P(h_src[1]), P(x4), T, E, S, F,
-                                        None if h_src[0] is None else P(h), P(self.rp_x), st), "vn_unreal_gather")
+        if not self.rp_skewed:  # (skewed: replayed pass only, h in place and rp_x = the appended maps)
+            _lib.check(lib.vn_unreal_gather(P(h_src[0]), P(h_src[1]), P(x4), T, E, S, F,
+                                            None if h_src[0] is None else P(h), P(self.rp_x), st), "vn_unreal_gather")
         n_pc = (T + 1) * S
         net.pc_forward(self.params, h, n_pc, self.pcb, self.pc_a1, self.pc_p2, None, self.pc_ws)
         H, W = self.env.frame_shape[:2]
@@ -471,8 +524,17 @@ class A2CTrainer:
                                                  ctypes.c_float(self.pc_weight), P(self.unreal_stats), st),
                    "vn_unreal_pc_loss_grad")
         net.pc_backward(self.params, h, n_pc, self.pcb, self.pc_a1, self.pc_p2, None, self.grads, self.dh_pc, self.pc_ws)
-        n_rp = (T - 2) * S
+        n_rp = self.rp_n
         net.rp_forward(self.params, self.rp_x, n_rp, self.rp_out)
+        if self.rp_skewed:
+            # the sampled windows: classes from the sampler's labels (-1 = a void draw); rp_dx is
+            # the appended slice of the replayed pass's dX4, so nothing is scattered
+            _lib.check(lib.vn_unreal_rp_loss_grad_labels(P(self.rp_out), P(self.rp_label), n_rp,
+                                                         ctypes.c_float(self.rp_weight), P(self.rp_dout),
+                                                         P(self.unreal_stats[1:3]), st),
+                       "vn_unreal_rp_loss_grad_labels")
+            net.rp_backward(self.params, self.rp_x, n_rp, self.rp_dout, self.grads, self.rp_dx, self.pc_ws)
+            return
         _lib.check(lib.vn_unreal_rp_loss_grad(P(self.rp_out), P(rewards), P(dones), T, E, S,
                                               ctypes.c_float(self.rp_weight), P(self.rp_dout),
                                               P(self.unreal_stats[1:3]), st), "vn_unreal_rp_loss_grad")
@@ -613,15 +675,26 @@ class A2CTrainer:
         n = (T + 1) * S
         u = self.ur_cur  # the slot vn_replay_push_draw drew this update
         rows = u["rows"]
-        frames = self._frames(rows[0], rows[1])
-        net.forward(self.params, frames, n, self.ur_acts, n, 0, None)
+        cap = self.ur_cap  # n, or with the skewed rp draw n + 3 rp_n: the sampled frames behind the slot's
+        if self.rp_skewed:
+            # this update's windows from the whole ring (after its push: the counter and the filled
+            # count are read on the device), their frame rows straight behind the slot's
+            P = _lib.ptr
+            _lib.check(self.lib.vn_unreal_rp_sample(ctypes.byref(self._rp_ring), self.rp_n,
+                                                    ctypes.c_double(self.rp_skew), self._rp_seed,
+                                                    P(self.rp_rows[0]), P(self.rp_rows[1]), P(self.rp_label),
+                                                    P(self.rp_src), P(self.rp_draw_stats), self._stream()),
+                       "vn_unreal_rp_sample")
+        frame_rows = self.ur_rows_ext if self.rp_skewed else rows
+        frames = self._frames(frame_rows[0], frame_rows[1])
+        net.forward(self.params, frames, cap, self.ur_acts, cap, 0, None)
         if self._merged_replay:  # the aux heads on the replayed rows t*E + e < T*E (aux_rows' frames)
             N = T * S
             self.aux_stats.zero_()
             net.aux_forward_loss_grad(self.params, self.ur_acts, n, N, self.a1, self.pred, self._aux_targets_replay,
                                       self.aux_weight, self.dpred, self.aux_stats, self.aux_ws)
             net.aux_backward(self.params, self.ur_acts, n, N, self.a1, self.dpred, self.grads, self.ur_dx4, self.aux_ws)
-        x5 = net.x5(self.ur_acts, n)
+        x5 = net.x5(self.ur_acts, cap)  # the LSTM and the heads run on the slot's n rows only
         h_r, c_r = self.ur_hc[0], self.ur_hc[1]
         h0, c0 = u["hc0"][0], u["hc0"][1]
         for t in range(T + 1):
@@ -636,14 +709,14 @@ class A2CTrainer:
         # the drawn slot's returns (V and the bootstrap from ur_out), then the heads' losses on
         # the replayed h (rows t*S + e, the bootstrap at t = T) and conv_base maps
         self._returns(rew, don, self.ur_out[T * S:], self.ur_out, T, S, self.ur_returns, replayed=True)
-        self._unreal_head_losses(net, self.ur_out, self.ur_returns, self.ur_dout, h_r, net.x4(self.ur_acts, n),
+        self._unreal_head_losses(net, self.ur_out, self.ur_returns, self.ur_dout, h_r, net.x4(self.ur_acts, cap),
                                  u["actions"], rew, don, rows[0], rows[0][T * S:], T, S, S, self.ur_dx4,
                                  self._merged_replay)
         # BPTT over the T + 1 replayed steps (value replay's dout + pixel control's dh), the trunk
         net.lstm_backward(self.params, T + 1, S, self.ur_dout, h_r, self.ur_xcat, self.ur_lacts, c_r, c0,
                           u["masks"], x5, self.ur_dz5, self.ur_grads, self.ur_lstm_ws, dh_extra=self.dh_pc,
                           extra_envs=S)
-        net.backward_ex(self.params, frames, n, self.ur_acts, n, None, self.ur_dz5, self.ur_dx4, self.ur_grads,
+        net.backward_ex(self.params, frames, cap, self.ur_acts, cap, None, self.ur_dz5, self.ur_dx4, self.ur_grads,
                         self.ur_ws)
 
     def _side_grad_range(self):
@@ -663,8 +736,11 @@ class A2CTrainer:
                                                "ur_lstm_ws", "h_pc", "pcb", "pc_a1", "pc_p2", "dh_pc", "pc_ws",
                                                "rp_x", "rp_dx", "rp_out", "rp_dout", "unreal_stats")]
         out += [("ur_cur." + k, v) for k, v in self.ur_cur.items()]
+        if self.rp_skewed:  # the sampler's outputs (rp_x / rp_dx above are slices of ur_acts / ur_dx4)
+            out += [(k, getattr(self, k)) for k in ("ur_rows_ext", "rp_label", "rp_src", "rp_draw_stats")]
         if self._merged_replay:
             out += [(k, getattr(self, k)) for k in ("a1", "pred", "dpred", "aux_ws", "aux_stats")]
+        out = [(k, t) for k, t in out if t is not None]  # (pc_a1: BigHouseModel's heads have no first layer)
         return out + [("grads[pc/rp]", self.grads[lo:hi])]
 
     def _main_owned(self):
@@ -1074,6 +1150,8 @@ class A2CTrainer:
             "curriculum": lambda: [self.cur_state[0].to(torch.float32).mean().reshape(1)],
             # the sums are exact in fp64 below 2^53: the vector turns fp64 here
             "shaping": lambda: [rsum(self.shape_stats[:2].to(f64)), self.shape_steps.to(f64)],
+            # counts below 2^24: exact in either width (the vector's: fp64 behind the shaping sums)
+            "rp_sampling": lambda: [rsum(self.rp_draw_stats.to(f64 if self.shaping else torch.float32))],
         }
         for name in list(layout)[1:]:
             parts = tails[name]()
@@ -1133,6 +1211,10 @@ class A2CTrainer:
             w = self.shaping_weight_at(steps)
             shaping = {"shaping_reward": w * (sb - float(np.float32(self.shaping_gamma)) * sa) / (N * self.world),
                        "shaping_weight": w}
+        rp = {}
+        if self.rp_skewed:  # the ring's candidates by reward and this update's draws, summed over ranks
+            rp = dict(zip(("rp_candidates_zero", "rp_candidates_nonzero", "rp_drawn_nonzero", "rp_drawn"),
+                          seg["rp_sampling"]))
         dt = time.perf_counter() - t0
         return {
             "step": self.total_steps, "updates": self.num_updates,
@@ -1150,6 +1232,7 @@ class A2CTrainer:
             **expert,
             **cur,
             **shaping,
+            **rp,
         }
 
     def run(self, log_every=10, logger=print):

@@ -2,7 +2,8 @@
 once: _update_metrics assembles the vector from it, step() decodes it by segment name. Pure Python."""
 
 
-def metric_layout(unreal=False, nav_metrics=False, expert=False, geo_curriculum=False, shaping=False):
+def metric_layout(unreal=False, nav_metrics=False, expert=False, geo_curriculum=False, shaping=False,
+                  rp_sampling=False):
     """{segment: (offset, width)} of the vector under these trainer flags, in the vector's order
     (its width: the last segment's offset + width). fp64 with ``shaping``, whose distance sums
     are exact there, fp32 otherwise."""
@@ -14,6 +15,9 @@ def metric_layout(unreal=False, nav_metrics=False, expert=False, geo_curriculum=
         ("expert", 4, expert),  # sum of -log q, agreeing samples, labelled samples, the weight used
         ("curriculum", 1, geo_curriculum),  # this rank's mean level over scenes
         ("shaping", 3, shaping),  # distance-before sum, distance-after sum, the anneal's step count
+        # the skewed reward-prediction draw (vn_unreal_rp_sample's stats4): zero-reward candidates,
+        # non-zero ones, draws with a non-zero reward, non-void draws
+        ("rp_sampling", 4, rp_sampling),
     )
     layout, offset = {}, 0
     for name, width, on in segments:

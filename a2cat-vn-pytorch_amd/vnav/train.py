@@ -131,6 +131,12 @@ class Experiment:
     shaping_gamma = 1.0
     shaping_anneal_steps = 0
     gae_lambda = 1.0
+    # the reward-prediction samples (A2CTrainer rp_sampling / rp_batch / rp_skew): "sequence" =
+    # the drawn rollout's own windows, "skewed" = rp_batch windows drawn from the whole replay
+    # ring with P(reward != 0) = rp_skew (needs unreal_source="replay"); batch None = unreal_envs
+    rp_sampling = "sequence"
+    rp_batch = None
+    rp_skew = 0.5
 
     def __init__(self, env_kwargs=None, model_kwargs=None, save_dir=None, seed=0, device=None, logger=print,
                  **overrides):
@@ -172,7 +178,8 @@ class Experiment:
                           expert_weight=self.expert_weight, expert_anneal_steps=self.expert_anneal_steps,
                           pg_coefficient=self.pg_coefficient, geo_curriculum=self.geo_curriculum,
                           shaping_weight=self.shaping_weight, shaping_gamma=self.shaping_gamma,
-                          shaping_anneal_steps=self.shaping_anneal_steps, gae_lambda=self.gae_lambda)
+                          shaping_anneal_steps=self.shaping_anneal_steps, gae_lambda=self.gae_lambda,
+                          rp_sampling=self.rp_sampling, rp_batch=self.rp_batch, rp_skew=self.rp_skew)
 
     def _setup(self):
         if self.trainer is None:
@@ -513,6 +520,8 @@ def main(argv=None):
                    help="fixed-set --test: the time limit of an evaluation episode (default: the env's)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--cuda-graph", action="store_true", help="replay each update as a captured hipGraph (1 GPU)")
+    p.add_argument("--no-cuda-graph", action="store_true",
+                   help="run every update eagerly, also where the experiment captures it by default")
     p.add_argument("--resume", action="store_true", help="continue from the checkpoint in --save-dir")
     p.add_argument("--nav-metrics", action="store_true",
                    help="log success_rate and spl of the finished episodes while training (--test always does)")
@@ -541,7 +550,23 @@ def main(argv=None):
                    help="anneal the shaping weight linearly to 0 over STEPS env-steps (default: constant)")
     p.add_argument("--gae-lambda", type=float, default=None, metavar="L",
                    help="GAE(lambda) advantages and lambda-return critic targets (default 1: n-step returns)")
+    p.add_argument("--rp-sampling", default=None, choices=("sequence", "skewed"),
+                   help="reward-prediction samples: the drawn rollout's windows (sequence, the default) or windows "
+                        "drawn from the whole replay ring with P(reward != 0) = --rp-skew (skewed; needs the UNREAL "
+                        "losses on replayed sequences)")
+    p.add_argument("--rp-batch", type=int, default=None, metavar="N",
+                   help="--rp-sampling skewed: windows per update (default: the UNREAL losses' env count)")
+    p.add_argument("--rp-skew", type=float, default=None, metavar="P",
+                   help="--rp-sampling skewed: the probability of a non-zero-reward window (default 0.5)")
     a = p.parse_args(argv)
+    if a.cuda_graph and a.no_cuda_graph:
+        p.error("--cuda-graph and --no-cuda-graph exclude each other")
+    if a.rp_sampling != "skewed" and (a.rp_batch is not None or a.rp_skew is not None):
+        p.error("--rp-batch / --rp-skew need --rp-sampling skewed")
+    if a.rp_batch is not None and a.rp_batch < 1:
+        p.error("--rp-batch must be at least 1")
+    if a.rp_skew is not None and not 0.0 <= a.rp_skew <= 1.0:
+        p.error("--rp-skew must lie in [0, 1]")
     if a.shaping_weight is None and (a.shaping_gamma is not None or a.shaping_anneal is not None):
         p.error("--shaping-gamma / --shaping-anneal need --shaping-weight")
     if a.gae_lambda is not None and not 0.0 <= a.gae_lambda <= 1.0:
@@ -567,6 +592,11 @@ def main(argv=None):
         over["max_time_steps"] = a.max_time_steps
     if a.cuda_graph:
         over["cuda_graph"] = True
+    if a.no_cuda_graph:
+        over["cuda_graph"] = False
+    for key, v in (("rp_sampling", a.rp_sampling), ("rp_batch", a.rp_batch), ("rp_skew", a.rp_skew)):
+        if v is not None:
+            over[key] = v
     if a.nav_metrics:
         over["nav_metrics"] = True
     if a.imitation:

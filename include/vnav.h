@@ -687,6 +687,42 @@ int vn_unreal_pc_loss_grad_ex(float* p2, int cells, const int32_t* actions, cons
  * or ts-1 are skipped. dlogits = weight * d mean CE / dlogits; stats2 = (mean CE, count). */
 int vn_unreal_rp_loss_grad(const float* logits, const float* rewards, const uint8_t* dones, int T, int E, int S,
                            float weight, float* dlogits, float* stats2, vn_stream_t stream);
+/* The same loss on explicit labels: label[j] = 0 / 1 / 2 is sample j's class, any other value
+ * (-1 by convention) leaves it unused (dlogits row 0, not counted). Same thread mapping and
+ * reduction order as vn_unreal_rp_loss_grad: equal logits under equivalent labels give equal
+ * bits. stats2 = (mean CE over the used samples, used count). VN_EINVAL: a NULL buffer, n <= 0. */
+int vn_unreal_rp_loss_grad_labels(const float* logits /* [n][4] */, const int32_t* label /* [n], -1 = unused */,
+                                  int n, float weight, float* dlogits, float* stats2, vn_stream_t stream);
+
+/* Reward-skewed reward-prediction draw from the replay ring (UNREAL's P(r != 0) = skew; DESIGN.md
+ * "Reward-skewed reward prediction"). The ring is the trainer's: the first S envs' record of
+ * every stored rollout and vn_replay_push_draw's meta, all read on the device.
+ *
+ * Candidates: windows (r, ts, e), r < min(meta4[1], capacity), 2 <= ts < T, e < S, with
+ * dones[r][ts-2][e] == 0 and dones[r][ts-1][e] == 0; index i = (r (T-2) + (ts-2)) S + e. Q0 =
+ * the candidates with rewards[r][ts][e] == 0 (-0.0 included), Q1 = the rest, both ordered by i.
+ * Draw j: R = Philox4x32-10((j, c_lo, c_hi, STREAM_RP = 6), key = seed), c = meta4[2];
+ * k = (R.x < (uint64)(skew * 2^32)) ? 1 : 0; an empty Qk gives k = 1 - k; both empty: the draw
+ * is void (label = src = -1, all six rows 0). Else idx = ((R.y 2^32 + R.z) |Qk|) >> 64 and the
+ * sample is Qk's idx-th element: rows_img[j][m] = rows[r][0][(ts-2+m) S + e], rows_goal[j][m] =
+ * rows[r][1][...], m = 0..2; label = 0 (reward == 0), 1 (> 0), 2 (< 0); src = i. With replacement.
+ * stats4 is written: [|Q0|, |Q1|, draws with label > 0, non-void draws]. The ring and meta are only
+ * read; no host value varies per call and nothing synchronises, so a captured graph replays it.
+ * One launch of one workgroup; capacity * (T - 2) * S <= VN_RP_SAMPLE_MAX_CANDIDATES.
+ * VN_EINVAL, nothing written: a NULL pointer other than src, count <= 0, T < 3, S < 1,
+ * capacity < 1, skew outside [0, 1], more candidates than the limit. */
+#define VN_RP_SAMPLE_MAX_CANDIDATES 1048576
+typedef struct vn_rp_ring {
+  const float* rewards;  /* [capacity][T][S] */
+  const uint8_t* dones;  /* [capacity][T][S] */
+  const int32_t* rows;   /* [capacity][2][(T+1)*S]: image rows, then goal rows; row t*S + e, t = T the bootstrap */
+  const int64_t* meta4;  /* vn_replay_push_draw's meta: [1] filled slots, [2] draw counter */
+  int32_t capacity, T, S;
+} vn_rp_ring;
+int vn_unreal_rp_sample(const vn_rp_ring* ring, int count, double skew, uint64_t seed,
+                        int32_t* rows_img /* [count][3] */, int32_t* rows_goal /* [count][3] */,
+                        int32_t* label /* [count] */, int32_t* src /* [count], may be NULL */, int32_t* stats4,
+                        vn_stream_t stream);
 /* dx [(T-2)*S][3][fcin] (vn_rp_backward's input gradient) onto dx4 rows t*E + e, e < S
  * (stored, or added when accumulate != 0; other rows untouched). */
 int vn_unreal_rp_scatter(const float* dx, int T, int E, int S, int fcin, float* dx4, int accumulate,
