@@ -40,6 +40,7 @@
 #include "vn_nav.h"
 #include "vn_shaping.h"
 #include "vn_unit_float.h"
+#include "vn_visit.h"
 
 namespace vn {
 
@@ -1114,6 +1115,8 @@ struct vn_ctx {
   std::vector<SceneDev> scenes_spd;
   // vn_nav_progress: the per-env progress record and its outputs (vn_shaping.hip)
   ShapeState* shape = nullptr;
+  // vn_visit_enable: the visit table, the per-env seen-sets and their outputs (vn_visit.hip)
+  VisitState* visit = nullptr;
 };
 
 namespace {
@@ -1167,6 +1170,10 @@ EnvArgs make_args(vn_ctx* c) {
 // the step, so where the caller set none the nav state's own arrays stand in and env_kernel
 // writes them as it would a caller's.
 void nav_fill(vn_ctx* c, EnvArgs& a) {
+  if (c->visit) {  // the visit kernel reads done and terminal_state
+    if (!a.done) a.done = c->visit->s_done;
+    if (!a.info_term) a.info_term = c->visit->s_term;
+  }
   if (!c->nav) return;
   if (!a.done) a.done = c->nav->s_done;
   if (!a.info_trunc) a.info_trunc = c->nav->s_trunc;
@@ -1175,13 +1182,25 @@ void nav_fill(vn_ctx* c, EnvArgs& a) {
   if (c->shape && !a.info_term) a.info_term = c->shape->s_term;  // the progress kernel reads it
 }
 // After the step's env_kernel launch (rc = its result), on the same stream.
-int nav_after_step(vn_ctx* c, const EnvArgs& a, int rc, hipStream_t stream) {
+int nav_side_launches(vn_ctx* c, const EnvArgs& a, int rc, hipStream_t stream) {
   if (rc != VN_OK || !c->nav) return rc;
   rc = nav_launch(c->nav, NAV_FORM_STEP, c->recs, a.done, a.info_trunc, a.info_len, a.info_ret, stream);
   if (rc == VN_OK && c->shape)
     rc = shape_launch(c->shape, c->nav, SHAPE_FORM_STEP, c->recs, nullptr, a.done, a.info_trunc, a.info_term, stream);
   if (rc != VN_OK || !c->cur || c->cur->cfg.window <= 0) return rc;
   return cur_count_launch(c->cur, c->recs, a.done, a.info_trunc, 1, stream);
+}
+// The visit launch goes behind the step's other side launches and shares no data with them.
+int nav_after_step(vn_ctx* c, const EnvArgs& a, int rc, hipStream_t stream) {
+  rc = nav_side_launches(c, a, rc, stream);
+  if (rc != VN_OK || !c->visit) return rc;
+  return visit_launch(c->visit, VISIT_FORM_STEP, c->recs, nullptr, a.done, a.info_term, c->autoreset, 1, stream);
+}
+// The episodes of the envs a launch outside a step has started (vn_reset: the masked ones, each
+// counted at its start; vn_set_state: all, uncounted, since a restore follows).
+int visit_refresh(vn_ctx* c, int rc, const int32_t* mask, int add, hipStream_t stream) {
+  if (rc != VN_OK || !c->visit) return rc;
+  return visit_launch(c->visit, VISIT_FORM_REFRESH, c->recs, mask, nullptr, nullptr, 0, add, stream);
 }
 // The progress record of the envs a launch outside a step may have moved (vn_reset: the masked
 // ones; vn_set_state: all), from their records.
@@ -1316,6 +1335,7 @@ void free_ctx(vn_ctx* c) {
   nav_destroy(c->nav);
   cur_destroy(c->cur);
   shape_destroy(c->shape);
+  visit_destroy(c->visit);
   delete c;
 }
 
@@ -1478,11 +1498,12 @@ int vn_reset(vn_ctx* c, const int32_t* env_mask_dev, vn_stream_t stream) {
   DeviceGuard guard(c->device);
   EnvArgs a = make_args(c);
   a.mask = env_mask_dev;
-  const int rc = launch_env<MODE_RESET>(c, a, (hipStream_t)stream);
-  if (rc != VN_OK || !c->nav) return rc;
-  return cur_refresh(c, shape_refresh(c, nav_launch(c->nav, NAV_FORM_RESET, c->recs, nullptr, nullptr, nullptr,
+  int rc = launch_env<MODE_RESET>(c, a, (hipStream_t)stream);
+  if (rc == VN_OK && c->nav)
+    rc = cur_refresh(c, shape_refresh(c, nav_launch(c->nav, NAV_FORM_RESET, c->recs, nullptr, nullptr, nullptr,
                                                     nullptr, (hipStream_t)stream),
                                       env_mask_dev, (hipStream_t)stream), (hipStream_t)stream);
+  return visit_refresh(c, rc, env_mask_dev, 1, (hipStream_t)stream);
 }
 
 int vn_observe(vn_ctx* c, uint8_t* obs_dev, uint8_t* goal_dev, int32_t* state_dev, vn_stream_t stream) {
@@ -1772,6 +1793,90 @@ int vn_set_nav_progress_state(vn_ctx* c, const int32_t* src, vn_stream_t stream)
   DeviceGuard guard(c->device);
   VN_HIP(hipMemcpyAsync(c->shape->rec, src, (size_t)c->n_envs * 12, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return VN_OK;
+}
+
+int vn_visit_enable(vn_ctx* c, int on) {
+  if (!c) return fail(VN_EINVAL, "vn_visit_enable: NULL ctx");
+  DeviceGuard guard(c->device);
+  VisitState* vs = nullptr;
+  if (on) {  // built first: a refusal leaves the context as it was
+    std::vector<int32_t> ns(c->n_scenes);
+    for (int k = 0; k < c->n_scenes; ++k) ns[k] = c->scenes_host[k].n;
+    int rc = visit_create(&vs, c->n_envs, ns);
+    if (rc != VN_OK) return rc;
+    // every env's episode from its current state: a running episode is covered from here
+    rc = visit_launch(vs, VISIT_FORM_REFRESH, c->recs, nullptr, nullptr, nullptr, 0, 1, 0);
+    if (rc != VN_OK) {
+      visit_destroy(vs);
+      return rc;
+    }
+  }
+  const hipError_t e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    visit_destroy(vs);
+    return hip_fail(e, "vn_visit_enable");
+  }
+  visit_destroy(c->visit);
+  c->visit = vs;
+  return VN_OK;
+}
+
+int vn_set_visit_outputs(vn_ctx* c, int32_t* cell, uint8_t* first, int32_t* ep_distinct) {
+  if (!c) return fail(VN_EINVAL, "vn_set_visit_outputs: NULL ctx");
+  if (!c->visit) return fail(VN_ESTATE, "vn_set_visit_outputs: visit counts are not enabled (vn_visit_enable)");
+  c->visit->cell_out = cell;
+  c->visit->first_out = first;
+  c->visit->ep_distinct_out = ep_distinct;
+  return VN_OK;
+}
+
+int vn_visit_table(vn_ctx* c, int scene, const uint32_t** count_dev, int32_t* n) {
+  if (!c || scene < 0 || scene >= c->n_scenes) return fail(VN_EINVAL, "vn_visit_table: bad args");
+  if (!c->visit) return fail(VN_ESTATE, "vn_visit_table: visit counts are not enabled (vn_visit_enable)");
+  if (count_dev) *count_dev = c->visit->count + c->visit->cell_off_host[scene];
+  if (n) *n = (int32_t)(c->visit->cell_off_host[scene + 1] - c->visit->cell_off_host[scene]);
+  return VN_OK;
+}
+
+int vn_visit_cells(vn_ctx* c, const uint32_t** count_dev, const int64_t** cell_off_dev, int64_t* cells) {
+  if (!c) return fail(VN_EINVAL, "vn_visit_cells: NULL ctx");
+  if (!c->visit) return fail(VN_ESTATE, "vn_visit_cells: visit counts are not enabled (vn_visit_enable)");
+  if (count_dev) *count_dev = c->visit->count;
+  if (cell_off_dev) *cell_off_dev = c->visit->cell_off;
+  if (cells) *cells = c->visit->C;
+  return VN_OK;
+}
+
+int vn_visit_get_state(vn_ctx* c, int32_t* dst, vn_stream_t stream) {
+  if (!c || !dst) return fail(VN_EINVAL, "vn_visit_get_state: NULL argument");
+  if (!c->visit) return fail(VN_ESTATE, "vn_visit_get_state: visit counts are not enabled (vn_visit_enable)");
+  DeviceGuard guard(c->device);
+  VN_HIP(hipMemcpyAsync(dst, c->visit->count, (size_t)c->visit->state_words() * 4, hipMemcpyDeviceToDevice,
+                        (hipStream_t)stream));
+  return VN_OK;
+}
+
+int vn_visit_set_state(vn_ctx* c, const int32_t* src, vn_stream_t stream) {
+  if (!c || !src) return fail(VN_EINVAL, "vn_visit_set_state: NULL argument");
+  if (!c->visit) return fail(VN_ESTATE, "vn_visit_set_state: visit counts are not enabled (vn_visit_enable)");
+  DeviceGuard guard(c->device);
+  VN_HIP(hipMemcpyAsync(c->visit->count, src, (size_t)c->visit->state_words() * 4, hipMemcpyDeviceToDevice,
+                        (hipStream_t)stream));
+  return VN_OK;
+}
+
+int vn_visit_clear(vn_ctx* c, vn_stream_t stream) {
+  if (!c) return fail(VN_EINVAL, "vn_visit_clear: NULL ctx");
+  if (!c->visit) return fail(VN_ESTATE, "vn_visit_clear: visit counts are not enabled (vn_visit_enable)");
+  DeviceGuard guard(c->device);
+  return visit_clear(c->visit, c->recs, (hipStream_t)stream);
+}
+
+int vn_visit_stats(vn_ctx* c, int scene, int64_t* stats2_dev, vn_stream_t stream) {
+  if (!c || !stats2_dev || scene < -1 || scene >= c->n_scenes) return fail(VN_EINVAL, "vn_visit_stats: bad args");
+  if (!c->visit) return fail(VN_ESTATE, "vn_visit_stats: visit counts are not enabled (vn_visit_enable)");
+  DeviceGuard guard(c->device);
+  return visit_stats(c->visit, scene, stats2_dev, (hipStream_t)stream);
 }
 
 int vn_nav_episode_stats(vn_ctx* c, float* stats4, vn_stream_t stream) {
@@ -2074,7 +2179,8 @@ int vn_set_state(vn_ctx* c, const int32_t* src, vn_stream_t stream) {
   hipLaunchKernelGGL(set_state_kernel, dim3((c->n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, c->recs,
                      c->n_envs, src, c->scenes, c->n_scenes, c->graph);
   VN_HIP(hipGetLastError());
-  return cur_refresh(c, shape_refresh(c, VN_OK, nullptr, (hipStream_t)stream), (hipStream_t)stream);
+  return visit_refresh(c, cur_refresh(c, shape_refresh(c, VN_OK, nullptr, (hipStream_t)stream), (hipStream_t)stream),
+                       nullptr, 0, (hipStream_t)stream);
 }
 
 int vn_get_episode_returns(vn_ctx* c, float* dst, vn_stream_t stream) {

@@ -202,6 +202,14 @@ SIGNATURES = {
     "vn_nav_curriculum_get_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vn_nav_curriculum_set_state": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vn_nav_curriculum_tables": (c_int, [c_void_p, c_int, P(c_void_p), P(c_void_p), P(c_int32), P(c_int32)]),
+    "vn_visit_enable": (c_int, [c_void_p, c_int]),
+    "vn_set_visit_outputs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vn_visit_table": (c_int, [c_void_p, c_int, P(c_void_p), P(c_int32)]),
+    "vn_visit_cells": (c_int, [c_void_p, P(c_void_p), P(c_void_p), P(c_int64)]),
+    "vn_visit_get_state": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vn_visit_set_state": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vn_visit_clear": (c_int, [c_void_p, c_void_p]),
+    "vn_visit_stats": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
 }
 
 SIGNATURES.update({
@@ -268,6 +276,8 @@ SIGNATURES.update({
                                       c_int, c_float, c_void_p, c_void_p]),
     "vn_a2c_returns_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
                                   c_float, c_float, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "vn_a2c_novelty_rewards": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float,
+                                       c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "vn_a2c_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int,
                                         c_float, c_float, c_void_p, c_void_p,
                                         c_void_p]),

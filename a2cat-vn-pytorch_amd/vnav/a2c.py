@@ -69,7 +69,8 @@ class A2CTrainer:
                  unreal=False, pc_weight=0.05, rp_weight=1.0, vr_weight=1.0, pc_gamma=0.9, unreal_envs=16,
                  unreal_source="rollout", nav_metrics=False, expert_weight=None, expert_anneal_steps=0,
                  pg_coefficient=1.0, geo_curriculum=None, shaping_weight=None, shaping_gamma=1.0,
-                 shaping_anneal_steps=0, gae_lambda=1.0, rp_sampling="sequence", rp_batch=None, rp_skew=0.5):
+                 shaping_anneal_steps=0, gae_lambda=1.0, rp_sampling="sequence", rp_batch=None, rp_skew=0.5,
+                 novelty_weight=0.0, first_visit_weight=0.0, novelty_anneal_steps=0):
         self.env = env
         self.lib = _lib.load()
         # check before every replayed UNREAL pass that the side stream's buffers and gradient
@@ -225,8 +226,35 @@ class A2CTrainer:
                 raise ValueError("rp_skew must lie in [0, 1], got %r" % (rp_skew,))
             if self.rp_batch is not None and self.rp_batch < 1:
                 raise ValueError("rp_batch must be at least 1, got %r" % (rp_batch,))
+        # novelty_weight / first_visit_weight (both 0 = off): the returns of the update are formed
+        # from rewards_aug = reward + w_count / sqrt(N(s)) + w_first [first visit of the episode]
+        # (vn_a2c_novelty_rewards, DESIGN.md "Visit counts and novelty bonus"), N the env's visit
+        # table at the end of the rollout, both weights annealed linearly to 0 over
+        # novelty_anneal_steps env steps (0: constant). visit_cell / visit_first [T, E]: step t's
+        # visit launch writes slot t. Everything else stays on the env's own reward: episode
+        # returns, the LSTM's last-reward input, the UNREAL labels and the replay ring. With both
+        # weights 0 nothing is allocated and no launch is added.
+        self.novelty_weight = float(novelty_weight)
+        self.first_visit_weight = float(first_visit_weight)
+        self.novelty_anneal_steps = int(novelty_anneal_steps)
+        if self.novelty_weight < 0 or self.first_visit_weight < 0:
+            raise ValueError("novelty_weight and first_visit_weight must be >= 0, got %r, %r"
+                             % (novelty_weight, first_visit_weight))
+        if self.novelty_anneal_steps < 0:
+            raise ValueError("novelty_anneal_steps must be >= 0, got %r" % (novelty_anneal_steps,))
+        self.novelty = self.novelty_weight != 0.0 or self.first_visit_weight != 0.0
+        if self.novelty:
+            if not env.visit_counts:
+                env.set_visit_counts(True)
+            self.visit_cell = torch.zeros((T, E), dtype=torch.int32, **kw)
+            self.visit_first = torch.zeros((T, E), dtype=torch.bool, **kw)
+            self.rewards_aug = torch.zeros((T, E), dtype=torch.float32, **kw)
+            self.novelty_stats = torch.zeros(4, dtype=torch.float32, **kw)
+            self.novelty_steps = torch.zeros(1, dtype=torch.int64, **kw)
+            self.visit_seen = torch.zeros(2, dtype=torch.int64, **kw)  # [states seen, visits] of this rank
         self._metric_layout = metric_layout(bool(unreal), self.nav_metrics, self.expert, self.geo_curriculum is not None,
-                                            self.shaping, self.rp_skewed)  # step()'s vector: {segment: (offset, width)}
+                                            self.shaping, self.rp_skewed,
+                                            self.novelty)  # step()'s vector: {segment: (offset, width)}
         self.workspace = torch.empty(self.net.workspace_floats(N), dtype=torch.float32, **kw)
         if self.recurrent:
             X = self.net.lstm["xcat"]
@@ -596,6 +624,20 @@ class A2CTrainer:
             c_float(self.gae_lambda), c_float(self.shaping_weight), c_float(self.shaping_gamma), P(self.shape_steps),
             ctypes.c_int64(self.shaping_anneal_steps), P(returns), P(stats), st), "vn_a2c_returns_ex")
 
+    def _novelty_rewards(self):
+        """rewards_aug of the rollout just sampled: one vn_a2c_novelty_rewards launch on the visit
+        histories and the env's table as it stands, and the table's statistics for the metrics.
+        The input of the returns only: self.rewards stays the env's own."""
+        P, c_float, env, T = _lib.ptr, ctypes.c_float, self.env, self.num_steps
+        count, _, cells = env.visit_cells()
+        _lib.check(self.lib.vn_a2c_novelty_rewards(
+            P(self.rewards), P(self.visit_cell), P(self.visit_first), ctypes.c_void_p(count), ctypes.c_int64(cells), T,
+            env.num_envs, c_float(self.novelty_weight), c_float(self.first_visit_weight), P(self.novelty_steps),
+            ctypes.c_int64(self.novelty_anneal_steps), P(self.rewards_aug), P(self.novelty_stats), self._stream()),
+            "vn_a2c_novelty_rewards")
+        env.visit_stats(out=self.visit_seen)
+        return self.rewards_aug
+
     def shaping_weight_at(self, steps):
         """The annealed shaping weight at an env-step count, as the device forms it: fp64, rounded
         once to fp32."""
@@ -748,7 +790,7 @@ class A2CTrainer:
         lo, _ = self._side_grad_range()
         names = ("acts", "workspace", "dout", "returns", "stats", "out", "dz5", "dx4", "lstm_ws", "xcat", "lstm_acts",
                  "aux_acts", "aux_out", "aux_dz5", "aux_grads", "unreal_dx4", "norm_partial", "scalars", "_hc0", "h_all",
-                 "c_all", "goal_list", "goal_run_length", "goal_count")
+                 "c_all", "goal_list", "goal_run_length", "goal_count", "rewards_aug", "novelty_stats", "visit_seen")
         if not self._merged_replay:
             names += ("a1", "pred", "dpred", "aux_ws", "aux_stats")
         out = [(k, getattr(self, k)) for k in names if isinstance(getattr(self, k, None), torch.Tensor)]
@@ -894,6 +936,8 @@ class A2CTrainer:
             self.expert_steps.copy_(self.sched[1:2])
         if self.returns_ex:  # the step count the shaping weight's anneal reads, as the expert's
             self.shape_steps.copy_(self.sched[1:2])
+        if self.novelty:  # and the novelty weights' anneal
+            self.novelty_steps.copy_(self.sched[1:2])
         self._rollout_begin()
         for t in range(T):
             sl = slice(t * E, (t + 1) * E)
@@ -903,12 +947,16 @@ class A2CTrainer:
                 env.set_nav_mask_output(self.expert_mask[t + 1] if t + 1 < T else None)
             if self.shaping:  # this step's distances before and after it: slot t
                 env.set_nav_progress_outputs(self.shape_dist[t, 0], self.shape_dist[t, 1])
+            if self.novelty:  # this step's arrival cell and first-visit flag: slot t
+                env.set_visit_outputs(self.visit_cell[t], self.visit_first[t], None)
             # one launch: the categorical draw from out[t] (Philox counter = updates * T + t from
             # the device schedule), the index-only env step, and the next step's recurrent
             # inputs, carries and episode statistics
             env.step_a2c(self._a2c_steps[t], self.rewards[t], self.dones[t], self.states)
         if self.shaping:  # steps outside a rollout (an evaluation) write the env's own buffers
             env.set_nav_progress_outputs(None, None)
+        if self.novelty:
+            env.set_visit_outputs(None, None, None)
         _lib.check(lib.vn_a2c_episode_stats(_lib.ptr(self.stats_env), E, _lib.ptr(self.episode_stats), self._stream()),
                    "vn_a2c_episode_stats")
         if self.nav_metrics:
@@ -946,7 +994,8 @@ class A2CTrainer:
                 with torch.cuda.stream(self._side_u):
                     self._unreal_replay_losses()
                     self._ev_u1.record(self._side_u)
-        self._returns(self.rewards, self.dones, self.boot_out, self.out, T, E, self.returns)
+        self._returns(self._novelty_rewards() if self.novelty else self.rewards, self.dones, self.boot_out, self.out,
+                      T, E, self.returns)
         if self.expert:  # the same launch shape, with the expert term: the update gains no launch
             _lib.check(lib.vn_a2c_loss_grad_expert(
                 _lib.ptr(self.out), _lib.ptr(self.actions), _lib.ptr(self.returns), _lib.ptr(self.expert_mask), N, A,
@@ -1152,6 +1201,9 @@ class A2CTrainer:
             "shaping": lambda: [rsum(self.shape_stats[:2].to(f64)), self.shape_steps.to(f64)],
             # counts below 2^24: exact in either width (the vector's: fp64 behind the shaping sums)
             "rp_sampling": lambda: [rsum(self.rp_draw_stats.to(f64 if self.shaping else torch.float32))],
+            # the bonus sums over ranks; the table is this rank's own (tables are not reduced)
+            "novelty": lambda: [rsum(self.novelty_stats[:2].to(f64 if self.shaping else torch.float32)),
+                                self.visit_seen[:1].to(f64 if self.shaping else torch.float32)],
         }
         for name in list(layout)[1:]:
             parts = tails[name]()
@@ -1215,6 +1267,11 @@ class A2CTrainer:
         if self.rp_skewed:  # the ring's candidates by reward and this update's draws, summed over ranks
             rp = dict(zip(("rp_candidates_zero", "rp_candidates_nonzero", "rp_drawn_nonzero", "rp_drawn"),
                           seg["rp_sampling"]))
+        novelty = {}
+        if self.novelty:  # the mean bonus per env step, the share of first visits, this rank's covered states
+            added, firsts, seen = seg["novelty"]
+            novelty = {"novelty_bonus": added / (N * self.world), "first_visit_rate": firsts / (N * self.world),
+                       "states_seen": seen}
         dt = time.perf_counter() - t0
         return {
             "step": self.total_steps, "updates": self.num_updates,
@@ -1233,6 +1290,7 @@ class A2CTrainer:
             **cur,
             **shaping,
             **rp,
+            **novelty,
         }
 
     def run(self, log_every=10, logger=print):

@@ -14,6 +14,9 @@ ENV_STATE = (
     ("env_nav", lambda tr: tr.nav_metrics, "get_nav_state", "set_nav_state"),
     ("env_curriculum", lambda tr: tr.geo_curriculum is not None, "curriculum_state", "set_curriculum_state"),
     ("env_nav_progress", lambda tr: tr.shaping, "get_nav_progress_state", "set_nav_progress_state"),
+    # the visit table, the episode records and the seen bitmaps, whoever switched the counts on
+    # (set_state has started every record again, uncounted)
+    ("env_visits", lambda tr: getattr(tr.env, "visit_counts", False), "get_visit_state", "set_visit_state"),
 )
 
 
@@ -51,6 +54,9 @@ def _without_env_table(tr, key):
     elif key == "env_nav_progress":  # set_state has started the record from the restored states
         warnings.warn("checkpoint holds no progress state (saved without shaping_weight): the running "
                       "episodes' distances start from their current positions")
+    elif key == "env_visits":  # set_state has started the records; the table keeps what it holds
+        warnings.warn("checkpoint holds no visit state (saved without visit counts): the table is not "
+                      "restored and the running episodes' coverage starts from their current positions")
     else:
         raise KeyError(key)
 

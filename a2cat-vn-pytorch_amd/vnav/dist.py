@@ -7,7 +7,9 @@ with the LSTM / aux / UNREAL heads), one flat bucket by default (A2CTrainer
 allreduce_buckets=1). allreduce_buckets=2 is opt-in: heads + LSTM + aux heads as soon as the
 LSTM backward ends, overlapped with the trunk backward, then the trunk — bitwise equal to
 one bucket in the gloo world-2 test, not yet run under RCCL across distinct GPUs. Plus one
-tiny all-reduce of the episode/loss statistics.
+tiny all-reduce of the episode/loss statistics. Per-env device state stays per rank: the
+curriculum levels and the visit tables (VectorEnv(visit_counts=True)) count this rank's envs
+alone and are not reduced, so `states_seen` is a rank's own figure.
 The reference has no distributed code at all (it runs 4 SubprocVecEnv processes on
 one GPU, experiments/thor_cached_auxiliary.py:58-71).
 """

@@ -39,6 +39,15 @@ NAV_KEYS = (("distance_to_goal", torch.int32), ("optimal_action", torch.int32), 
             ("success", torch.bool), ("spl", torch.float32), ("start_distance", torch.int32))
 # info keys of nav_progress=True (set_nav_progress), both int32
 PROGRESS_KEYS = ("distance_before", "progress")
+# info keys of visit_counts=True (set_visit_counts), in vn_set_visit_outputs' order
+VISIT_KEYS = (("visit_cell", torch.int32), ("first_visit", torch.bool), ("coverage", torch.int32))
+
+
+class _DeviceWords:
+    """A span of 32-bit words in device memory the library owns, for torch.as_tensor."""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = dict(shape=(int(n),), typestr="<i4", data=(int(ptr), False), version=2)
 
 
 def to_float_chw(frames):
@@ -73,7 +82,8 @@ class VectorEnv:
 
     def __init__(self, scenes, num_envs, seed=0, device=None, max_episode_steps=900, tasks=None,
                  env_scenes=None, autoreset=True, aux_observations=False, reuse_outputs=True,
-                 obs_format="u8_hwc", aux_format=None, nav_info=False, image_size=None, nav_progress=False):
+                 obs_format="u8_hwc", aux_format=None, nav_info=False, image_size=None, nav_progress=False,
+                 visit_counts=False):
         """obs_format: "u8_hwc" (default) returns and takes uint8 [E,H,W,C] frames; "f32_chw"
         returns and takes float32 [E,C,H,W] frames in [0, 1], every value float(u8) / 255 as
         fp32 division (ScaledFloatFrame's), converted in the step's own launch with the same
@@ -91,6 +101,9 @@ class VectorEnv:
         distance to the goal before the step) and ``progress`` (how many actions closer the step
         brought the env, 0 where the goal is unreachable; ``set_nav_progress``). ``reward`` stays
         the environment's own.
+        visit_counts: keep a visit count per (scene, state) and the running episode's set of
+        seen states on the device (``set_visit_counts``; needs no nav_info): every step's info
+        also carries ``visit_cell``, ``first_visit`` and, per finished episode, ``coverage``.
         image_size: (height, width) of the frames the env emits, the reference cached env's
         ``image_size`` (cached.py:19,62-64). Every scene whose frames have another size is
         resized on the device before the scene cache is built (``scenes.resize_scene``); None
@@ -152,6 +165,8 @@ class VectorEnv:
         self.nav_info = False
         self.nav_progress = False
         self._progress_home = (None, None)
+        self.visit_counts = False
+        self._visit_home = (None, None, None)
         self.episode_log = None
         self.geo_curriculum = None  # set_geodesic_curriculum's configuration while it is on
         # the env -> scene assignment (vn_set_env_scenes; the native default)
@@ -211,6 +226,8 @@ class VectorEnv:
             if not nav_info:
                 raise ValueError("nav_progress=True needs nav_info=True")
             self.set_nav_progress(True)
+        if visit_counts:
+            self.set_visit_counts(True)
 
     def _build_aux_arena(self):
         """Depth [rows,H,W,1] and segmentation [rows,H,W,3] uint8 on the device, indexed by
@@ -417,6 +434,120 @@ class VectorEnv:
         buf = buf.to(device=self.device, dtype=torch.int32).contiguous()
         _lib.check(self.lib.vn_set_nav_progress_state(self._ctx, _lib.ptr(buf), self._stream()),
                    "vn_set_nav_progress_state")
+        buf.record_stream(torch.cuda.current_stream(self.device))
+
+    # -- visit counts (DESIGN.md "Visit counts and novelty bonus") ----------------
+    def _drop_visits(self):
+        self.visit_counts = False
+        self._visit_home = (None, None, None)
+        for k, _ in VISIT_KEYS:
+            self._info.pop(k, None)
+
+    def _need_visits(self):
+        if not self.visit_counts:
+            raise _lib.VnavError("visit counts are off: VectorEnv(..., visit_counts=True)")
+
+    def set_visit_counts(self, on, buffers=None):
+        """Enable / disable the visit counts (vn_visit_enable; independent of nav_info): the
+        device keeps a count per (scene, state) of how often an env arrived there, and per env
+        the set of states its running episode has seen. info gains ``visit_cell`` (int32: the
+        arrival state's index in the table of all scenes, ``visit_cells()``), ``first_visit``
+        (bool: the episode had not been there) and ``coverage`` (int32: the finished episode's
+        number of distinct states where ``done``, else 0). Episodes already running are covered
+        from their current state, which is counted once. ``buffers``: the caller's own tensors
+        in VISIT_KEYS' order, any may be None (not written); default the env's own. Replaces
+        launch arguments: a captured graph must be recaptured."""
+        if on:
+            if buffers is None:
+                buffers = [torch.zeros(self.num_envs, dtype=dt, device=self.device) for _, dt in VISIT_KEYS]
+            buffers = list(buffers)
+            if len(buffers) != len(VISIT_KEYS):
+                raise ValueError("visit buffers: one per key of %s" % ([k for k, _ in VISIT_KEYS],))
+            for (k, dt), t in zip(VISIT_KEYS, buffers):
+                self._check_out(k, t, dt, self.num_envs)
+        self.config_generation += 1
+        _lib.check(self.lib.vn_visit_enable(self._ctx, 1 if on else 0), "vn_visit_enable")
+        self._drop_visits()
+        if not on:
+            return
+        self.visit_counts = True
+        self._visit_home = tuple(buffers)
+        for (k, _), t in zip(VISIT_KEYS, buffers):
+            if t is not None:
+                self._info[k] = t
+        self.set_visit_outputs(None, None, None)
+
+    def set_visit_outputs(self, cell, first, coverage=None):
+        """Where the next steps write the visit outputs: [E] device tensors (int32, bool, int32),
+        e.g. a trainer's per-step slots (any None: not written). All three None: back to the
+        buffers set_visit_counts() was given (vn_set_visit_outputs: a pointer swap, no launch,
+        no sync). The caller keeps the tensors alive while steps may write them."""
+        self._need_visits()
+        if cell is None and first is None and coverage is None:
+            cell, first, coverage = self._visit_home
+        for (k, dt), t in zip(VISIT_KEYS, (cell, first, coverage)):
+            self._check_out(k, t, dt, self.num_envs)
+        _lib.check(self.lib.vn_set_visit_outputs(self._ctx, _lib.ptr(cell), _lib.ptr(first), _lib.ptr(coverage)),
+                   "vn_set_visit_outputs")
+
+    def visit_cells(self):
+        """(count pointer, cell_off pointer, C) of the table of all scenes (vn_visit_cells): raw
+        device addresses for the kernels, valid until the next set_visit_counts()."""
+        self._need_visits()
+        p, q, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        _lib.check(self.lib.vn_visit_cells(self._ctx, ctypes.byref(p), ctypes.byref(q), ctypes.byref(n)),
+                   "vn_visit_cells")
+        return p.value, q.value, n.value
+
+    def visit_table(self, scene_index):
+        """The live visit table of a scene: an int32 [n_states] view of the device memory the
+        steps count into (no copy; the table's words are unsigned, so a count of 2^31 or more
+        reads negative). Valid until the next set_visit_counts()."""
+        self._need_visits()
+        p, n = ctypes.c_void_p(), ctypes.c_int32()
+        _lib.check(self.lib.vn_visit_table(self._ctx, int(scene_index), ctypes.byref(p), ctypes.byref(n)),
+                   "vn_visit_table")
+        return torch.as_tensor(_DeviceWords(p.value, n.value), device=self.device)
+
+    def visit_stats(self, scene=None, out=None):
+        """int64 [2] device tensor: the number of states with a count > 0 and the sum of the
+        counts, of one scene or (None) of all (vn_visit_stats: exact integer sums)."""
+        self._need_visits()
+        if out is None:
+            out = torch.empty(2, dtype=torch.int64, device=self.device)
+        else:
+            self._check_out("visit stats", out, torch.int64, 2)
+        _lib.check(self.lib.vn_visit_stats(self._ctx, -1 if scene is None else int(scene), _lib.ptr(out),
+                                           self._stream()), "vn_visit_stats")
+        return out
+
+    def clear_visits(self):
+        """Zero the table and start every env's episode record from its current state
+        (vn_visit_clear: on the current stream, no host value, so it may be captured)."""
+        self._need_visits()
+        _lib.check(self.lib.vn_visit_clear(self._ctx, self._stream()), "vn_visit_clear")
+
+    def _visit_words(self):
+        W = (max(s.n_states for s in self.scenes) + 31) // 32
+        return sum(s.n_states for s in self.scenes) + self.num_envs * (2 + W)
+
+    def get_visit_state(self):
+        """The visit state a checkpoint needs, one flat int32 tensor: the counts of all scenes,
+        the [2, E] record (episode scene, distinct states) and the [E, W] seen bitmaps."""
+        self._need_visits()
+        buf = torch.empty(self._visit_words(), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.vn_visit_get_state(self._ctx, _lib.ptr(buf), self._stream()), "vn_visit_get_state")
+        return buf
+
+    def set_visit_state(self, buf):
+        """Restore get_visit_state()'s tensor; call it after set_state(), which starts every
+        env's episode record again from the states it sets."""
+        self._need_visits()
+        buf = torch.as_tensor(buf)
+        if tuple(buf.shape) != (self._visit_words(),):
+            raise ValueError("visit state must be [%d] (this env), got %s" % (self._visit_words(), tuple(buf.shape)))
+        buf = buf.to(device=self.device, dtype=torch.int32).contiguous()
+        _lib.check(self.lib.vn_visit_set_state(self._ctx, _lib.ptr(buf), self._stream()), "vn_visit_set_state")
         buf.record_stream(torch.cuda.current_stream(self.device))
 
     # -- fixed-episode evaluation (DESIGN.md "Fixed-episode evaluation") -------

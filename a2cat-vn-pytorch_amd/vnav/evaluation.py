@@ -10,7 +10,8 @@ from . import episodes as vep
 from .checkpoint import env_state, restore_env_state
 
 # the trainer's tensors that a fixed-episode evaluation's rollouts write, besides the recurrent carry
-_TRAINER_STATE = ("sched", "lr_dev", "stats_env", "episode_stats", "nav_stats", "shape_steps")
+_TRAINER_STATE = ("sched", "lr_dev", "stats_env", "episode_stats", "nav_stats", "shape_steps",
+                  "novelty_steps")
 
 
 def evaluate(tr, episodes=10, max_rollouts=10000):
@@ -25,6 +26,11 @@ def evaluate(tr, episodes=10, max_rollouts=10000):
     saved_sched = tr.sched.clone()  # sampling counter and step count: evaluation leaves both
     # the curriculum's counters see the rollouts below: levels, counters back afterwards
     saved_cur = tr.env.curriculum_state().clone() if tr.geo_curriculum is not None else None
+    # and the visit counts: the table, the records and the seen-sets come back bit for bit
+    # (meanwhile the table counts the evaluation alone: ``states_seen`` and ``coverage`` below)
+    saved_visits = tr.env.get_visit_state() if getattr(tr.env, "visit_counts", False) else None
+    if saved_visits is not None:
+        tr.env.clear_visits()
     tot = torch.zeros(7 if tr.nav_metrics else 3, dtype=torch.float64)
     agree = torch.zeros(2, dtype=torch.float64)  # agreeing, labelled samples
     for _ in range(int(max_rollouts)):
@@ -46,9 +52,14 @@ def evaluate(tr, episodes=10, max_rollouts=10000):
     tr.sched.copy_(saved_sched)
     if saved_cur is not None:
         tr.env.set_curriculum_state(saved_cur)
+    visits = {}
+    if saved_visits is not None:  # this rank's: the tables are per rank and are not reduced
+        seen = int(tr.env.visit_stats()[0])
+        visits = {"states_seen": seen, "coverage": seen / sum(s.n_states for s in tr.env.scenes)}
+        tr.env.set_visit_state(saved_visits)
     n, rsum, lsum = tot.tolist()[:3]
     out = {"episodes": n, "reward": rsum / n if n else float("nan"),
-           "episode_length": lsum / n if n else float("nan")}
+           "episode_length": lsum / n if n else float("nan"), **visits}
     if tr.nav_metrics:
         n_ep, n_ok, spl_sum, start_sum = tot.tolist()[3:]
         nan = float("nan")

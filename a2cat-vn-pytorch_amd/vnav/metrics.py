@@ -3,7 +3,7 @@ once: _update_metrics assembles the vector from it, step() decodes it by segment
 
 
 def metric_layout(unreal=False, nav_metrics=False, expert=False, geo_curriculum=False, shaping=False,
-                  rp_sampling=False):
+                  rp_sampling=False, novelty=False):
     """{segment: (offset, width)} of the vector under these trainer flags, in the vector's order
     (its width: the last segment's offset + width). fp64 with ``shaping``, whose distance sums
     are exact there, fp32 otherwise."""
@@ -18,6 +18,9 @@ def metric_layout(unreal=False, nav_metrics=False, expert=False, geo_curriculum=
         # the skewed reward-prediction draw (vn_unreal_rp_sample's stats4): zero-reward candidates,
         # non-zero ones, draws with a non-zero reward, non-void draws
         ("rp_sampling", 4, rp_sampling),
+        # the novelty bonus (vn_a2c_novelty_rewards' stats4 and vn_visit_stats): the sum of the
+        # added terms, the rollout's first visits, this rank's states with a count > 0
+        ("novelty", 3, novelty),
     )
     layout, offset = {}, 0
     for name, width, on in segments:

@@ -137,6 +137,13 @@ class Experiment:
     rp_sampling = "sequence"
     rp_batch = None
     rp_skew = 0.5
+    # the novelty bonus (A2CTrainer novelty_weight / first_visit_weight / novelty_anneal_steps):
+    # both weights 0 = off; visit_counts keeps the env's visit table without a bonus (test()
+    # then reports the evaluation's coverage)
+    novelty_weight = 0.0
+    first_visit_weight = 0.0
+    novelty_anneal_steps = 0
+    visit_counts = False
 
     def __init__(self, env_kwargs=None, model_kwargs=None, save_dir=None, seed=0, device=None, logger=print,
                  **overrides):
@@ -179,7 +186,9 @@ class Experiment:
                           pg_coefficient=self.pg_coefficient, geo_curriculum=self.geo_curriculum,
                           shaping_weight=self.shaping_weight, shaping_gamma=self.shaping_gamma,
                           shaping_anneal_steps=self.shaping_anneal_steps, gae_lambda=self.gae_lambda,
-                          rp_sampling=self.rp_sampling, rp_batch=self.rp_batch, rp_skew=self.rp_skew)
+                          rp_sampling=self.rp_sampling, rp_batch=self.rp_batch, rp_skew=self.rp_skew,
+                          novelty_weight=self.novelty_weight, first_visit_weight=self.first_visit_weight,
+                          novelty_anneal_steps=self.novelty_anneal_steps)
 
     def _setup(self):
         if self.trainer is None:
@@ -190,6 +199,8 @@ class Experiment:
                 # the VectorEnv constructor already reset, so draw the starts again
                 self.env.set_hardness(self.hardness)
                 self.env.reset()
+            if self.visit_counts and not self.env.visit_counts:
+                self.env.set_visit_counts(True)
             self.trainer = self.create_trainer()
         return self.trainer
 
@@ -558,7 +569,23 @@ def main(argv=None):
                    help="--rp-sampling skewed: windows per update (default: the UNREAL losses' env count)")
     p.add_argument("--rp-skew", type=float, default=None, metavar="P",
                    help="--rp-sampling skewed: the probability of a non-zero-reward window (default 0.5)")
+    p.add_argument("--novelty-weight", type=float, default=None, metavar="W",
+                   help="train on r + W / sqrt(N(s)), N the visit count of the state the step arrived in (the "
+                        "env's own reward and episode returns stay as they are)")
+    p.add_argument("--first-visit-weight", type=float, default=None, metavar="W",
+                   help="train on r + W at an episode's first visit of a state")
+    p.add_argument("--novelty-anneal", type=int, default=None, metavar="STEPS",
+                   help="anneal both novelty weights linearly to 0 over STEPS env-steps (default: constant)")
+    p.add_argument("--visit-counts", action="store_true",
+                   help="keep the per-state visit table on the device without a bonus; with --test, report the "
+                        "states the evaluation covered")
     a = p.parse_args(argv)
+    for flag, v in (("--novelty-weight", a.novelty_weight), ("--first-visit-weight", a.first_visit_weight),
+                    ("--novelty-anneal", a.novelty_anneal)):
+        if v is not None and v < 0:
+            p.error("%s must be >= 0" % flag)
+    if a.novelty_anneal is not None and not (a.novelty_weight or a.first_visit_weight):
+        p.error("--novelty-anneal needs --novelty-weight or --first-visit-weight")
     if a.cuda_graph and a.no_cuda_graph:
         p.error("--cuda-graph and --no-cuda-graph exclude each other")
     if a.rp_sampling != "skewed" and (a.rp_batch is not None or a.rp_skew is not None):
@@ -612,9 +639,13 @@ def main(argv=None):
     if a.geo_curriculum is not None:
         over["geo_curriculum"] = dict(cur, level=a.geo_curriculum)
     for key, v in (("shaping_weight", a.shaping_weight), ("shaping_gamma", a.shaping_gamma),
-                   ("shaping_anneal_steps", a.shaping_anneal), ("gae_lambda", a.gae_lambda)):
+                   ("shaping_anneal_steps", a.shaping_anneal), ("gae_lambda", a.gae_lambda),
+                   ("novelty_weight", a.novelty_weight), ("first_visit_weight", a.first_visit_weight),
+                   ("novelty_anneal_steps", a.novelty_anneal)):
         if v is not None:
             over[key] = v
+    if a.visit_counts:
+        over["visit_counts"] = True
     exp = make_trainer(a.name, env_kwargs=env_kwargs, save_dir=a.save_dir, seed=a.seed, **over)
     fixed = a.eval_episodes is not None or a.eval_set is not None
     if not fixed and (a.eval_buckets or a.greedy or a.save_eval_set or a.eval_max_steps is not None):

@@ -407,6 +407,59 @@ int vn_set_nav_progress_outputs(vn_ctx* ctx, int32_t* dist_before, int32_t* dist
 int vn_get_nav_progress_state(vn_ctx* ctx, int32_t* dst_dev_3xE, vn_stream_t stream);
 int vn_set_nav_progress_state(vn_ctx* ctx, const int32_t* src_dev_3xE, vn_stream_t stream);
 
+/* State-visit counts (DESIGN.md "Visit counts and novelty bonus"). Independent of vn_nav_enable:
+ * no geodesic table is needed. on = 1 allocates, on the device,
+ *   cell_off [n_scenes + 1] int64: the prefix sum of the scenes' state counts; state s of scene
+ *     k is cell cell_off[k] + s, and C = cell_off[n_scenes] (VN_EINVAL if C >= 2^31);
+ *   count [C] uint32, zeroed: how often an env arrived in the cell;
+ *   per env the scene of the running episode (ep_scene), the number of distinct states it has
+ *     been in (ep_distinct) and their bitmap seen[W], W = ceil(max n_states / 32) words;
+ * then starts every env from its current state (its bit set, ep_distinct = 1, its cell counted
+ * once). While it is on, vn_step / vn_step_f32 / vn_step_aux / vn_step_a2c launch one more small
+ * kernel behind their other side launches, a group of 8 lanes per env:
+ *   the arrival state is (ep_scene, terminal_state) where done (after an auto-reset the env
+ *     already holds the next episode), else the env's (scene, state); both are clamped into the
+ *     tables; cell = cell_off[scene] + state;
+ *   count[cell] += 1 (an atomic add whose old value is unused: the table after the launch is
+ *     exact and independent of order);
+ *   first = the state's bit was clear in seen; the bit is set and ep_distinct += first;
+ *   the outputs of vn_set_visit_outputs are written;
+ *   where done and auto-reset is on, the next episode starts: seen cleared, ep_scene = the env's
+ *     scene, the start state's bit set, ep_distinct = 1, and the start cell counted once.
+ * With auto-reset off (vn_set_autoreset(ctx, 0)) a done env's episode goes on: its seen-set and
+ * ep_distinct stay, later steps (the env keeps moving from where it stopped, terminal re-emit
+ * steps included) are counted into the same episode, and every done step reports ep_distinct;
+ * the episode starts with vn_reset. vn_reset starts the episode of the envs it reset, counting
+ * their start cells; vn_set_state starts every env's episode without counting (restore the
+ * visit state with vn_visit_set_state after it). terminal_state and done are read from the
+ * caller's buffers, or from stand-ins of the visit state where the caller set none.
+ * Synchronises and replaces launch arguments (a captured graph must be recaptured). A refusal
+ * leaves the context as it was. on = 0 frees everything. */
+int vn_visit_enable(vn_ctx* ctx, int on);
+/* Where the following visit launches write, [n_envs] on the device each, any may be NULL (not
+ * written): cell int32 (the arrival cell), first uint8 (1 = the episode's first visit of it),
+ * ep_distinct int32 (the finished episode's distinct states where done, else 0). A host-side
+ * pointer swap like vn_set_nav_progress_outputs: no launch, no synchronisation. The caller owns
+ * the buffers. VN_ESTATE before vn_visit_enable. */
+int vn_set_visit_outputs(vn_ctx* ctx, int32_t* cell, uint8_t* first, int32_t* ep_distinct);
+/* The live table of one scene ([*n] uint32), and of all scenes with its offsets ([*cells] uint32,
+ * [n_scenes + 1] int64): device pointers into the visit state, valid until vn_visit_enable.
+ * Any output pointer may be NULL. VN_ESTATE before vn_visit_enable. */
+int vn_visit_table(vn_ctx* ctx, int scene, const uint32_t** count_dev, int32_t* n);
+int vn_visit_cells(vn_ctx* ctx, const uint32_t** count_dev, const int64_t** cell_off_dev, int64_t* cells);
+/* The visit state a checkpoint needs, C + n_envs (2 + W) 32-bit words on the device: count [C],
+ * then the [2][n_envs] int32 record (ep_scene, ep_distinct), then seen [n_envs][W]. Stream-ordered
+ * copies; set after vn_set_state, which starts every episode again. */
+int vn_visit_get_state(vn_ctx* ctx, int32_t* dst_dev, vn_stream_t stream);
+int vn_visit_set_state(vn_ctx* ctx, const int32_t* src_dev, vn_stream_t stream);
+/* count = 0, then every env starts from its current state as vn_visit_enable starts it. On
+ * `stream`, with no host value: may be captured in a graph. */
+int vn_visit_clear(vn_ctx* ctx, vn_stream_t stream);
+/* stats2_dev, int64 [2] on the device, zeroed by the call: the number of cells with count > 0
+ * and the sum of the counts, of one scene or of all (scene = -1). Integer sums: the same bits
+ * from the same table. VN_EINVAL: NULL stats2_dev, scene outside -1 .. n_scenes - 1. */
+int vn_visit_stats(vn_ctx* ctx, int scene, int64_t* stats2_dev, vn_stream_t stream);
+
 /* Fixed-episode evaluation (DESIGN.md "Fixed-episode evaluation").
  * Draws `count` (start, goal) pairs of `scene`, with replacement, uniformly from
  * Q = {(g, s) : dist_lo <= geo[g][s] <= dist_hi}, Q ordered by g, then by s. Exact, so a host
@@ -816,6 +869,25 @@ int vn_a2c_returns_ex(const float* rewards, const uint8_t* dones, const float* b
                       const int32_t* dist, int T, int E, int num_actions, float gamma, float lambda, float weight,
                       float gamma_phi, const int64_t* steps_dev, int64_t anneal_steps, float* returns,
                       int64_t* stats3_dev, vn_stream_t stream);
+/* The novelty bonus of a rollout (DESIGN.md "Visit counts and novelty bonus"), one launch.
+ * rewards [T][E] f32 (never written), cell [T][E] int32 and first [T][E] uint8 (the histories
+ * of vn_set_visit_outputs), count [C] uint32 (vn_visit_cells) as it stands at the launch, i.e.
+ * at the end of the rollout. With wc = w_count and wf = w_first when anneal_steps <= 0, else
+ * each times max(0, 1 - *steps_dev / anneal_steps) in fp64 rounded once to fp32, read on the
+ * device by the launch (a captured update anneals), per element, N = count[cell]:
+ *   b = wc / sqrt(float(N)), 0 where cell < 0, cell >= C or N == 0;
+ *   f = wf where first, else 0;
+ *   rewards_out = r + (b + f);
+ * every operation one correctly rounded fp32 operation (a -0.0 reward with b = f = 0 becomes
+ * +0.0, IEEE's sum). stats4 [4] f32 on the device = (sum of b + f, number of first visits,
+ * sum of 1 / sqrt(float(N)) over the elements with N > 0, wc): fp64 sums in a fixed order
+ * rounded once, the same bits from the same inputs. rewards_out must not overlap rewards.
+ * VN_EINVAL, nothing written: a NULL rewards / cell /
+ * first / count / rewards_out / stats4, C < 0, T <= 0, E <= 0, anneal_steps > 0 without
+ * steps_dev. */
+int vn_a2c_novelty_rewards(const float* rewards, const int32_t* cell, const uint8_t* first, const uint32_t* count,
+                           int64_t C, int T, int E, float w_count, float w_first, const int64_t* steps_dev,
+                           int64_t anneal_steps, float* rewards_out, float* stats4, vn_stream_t stream);
 int vn_a2c_loss_grad(const float* out, const int32_t* actions, const float* returns, int n,
                      int num_actions, float value_coef, float entropy_coef, float* dout,
                      float* stats4, vn_stream_t stream);
