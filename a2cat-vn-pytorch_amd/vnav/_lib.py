@@ -314,6 +314,11 @@ SIGNATURES.update({
     "vn_a2c_episode_stats": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "vn_rmsprop_step_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_float,
                                     c_float, c_void_p]),
+    "vn_ppo_adv_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "vn_ppo_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float,
+                                 c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vn_adam_step_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p,
+                                 c_void_p, c_float, c_float, c_float, c_void_p]),
 })
 
 _lib = None

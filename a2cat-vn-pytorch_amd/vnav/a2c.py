@@ -58,6 +58,8 @@ from .policy import OUT_LD, AuxTargets, PolicyNet, frames_from_rows
 # rows at or below which vn_policy_heads takes its skinny path (kSkinnyRows, csrc/vn_skinny.h):
 # there the env-step launch computes the heads with the same sums (vn_a2c_step.head_weight)
 _FUSED_HEADS_MAX_ENVS = 16
+# eps of the PPO advantage normalisation (adv - mean) / (std + eps)
+_PPO_ADV_EPS = 1e-8
 
 
 class A2CTrainer:
@@ -70,7 +72,9 @@ class A2CTrainer:
                  unreal_source="rollout", nav_metrics=False, expert_weight=None, expert_anneal_steps=0,
                  pg_coefficient=1.0, geo_curriculum=None, shaping_weight=None, shaping_gamma=1.0,
                  shaping_anneal_steps=0, gae_lambda=1.0, rp_sampling="sequence", rp_batch=None, rp_skew=0.5,
-                 novelty_weight=0.0, first_visit_weight=0.0, novelty_anneal_steps=0):
+                 novelty_weight=0.0, first_visit_weight=0.0, novelty_anneal_steps=0, ppo_clip=None, ppo_epochs=4,
+                 ppo_value_clip=0.0, ppo_normalize_advantage=True, optimizer="rmsprop", adam_betas=(0.9, 0.999),
+                 adam_epsilon=1e-5):
         self.env = env
         self.lib = _lib.load()
         # check before every replayed UNREAL pass that the side stream's buffers and gradient
@@ -89,6 +93,38 @@ class A2CTrainer:
         self.seed = int(seed)
         self.group = process_group
         self.world, self.rank = vdist.world_of(process_group)
+        # ppo_clip (None = off): update() runs ppo_epochs full-batch epochs of the clipped surrogate
+        # over the stored rollout instead of one A2C step (_ppo_update, DESIGN.md "PPO epochs").
+        # Each combination refused here is out of scope, not impossible.
+        self.ppo = ppo_clip is not None
+        self.ppo_epochs = int(ppo_epochs)
+        self.ppo_value_clip = float(ppo_value_clip)
+        self.ppo_normalize_advantage = bool(ppo_normalize_advantage)
+        self._on_ppo_epoch = None
+        if self.ppo_epochs < 1:
+            raise ValueError("ppo_epochs must be at least 1, got %r" % (ppo_epochs,))
+        if self.ppo:
+            self.ppo_clip = float(ppo_clip)
+            if not self.ppo_clip > 0.0:
+                raise ValueError("ppo_clip must be > 0, got %r" % (ppo_clip,))
+            if self.world > 1:
+                raise ValueError("ppo_clip does not run at world > 1 yet: the advantage statistics would need a "
+                                 "cross-rank reduction")
+            if unreal:
+                raise ValueError("ppo_clip does not run with unreal=True yet: the UNREAL losses have no epoch loop")
+            if aux_source == "replay":
+                raise ValueError("ppo_clip does not run with aux_source='replay' yet: the replayed aux batch has its "
+                                 "own trunk pass, which the epochs do not repeat")
+            if expert_weight is not None:
+                raise ValueError("ppo_clip does not run with expert_weight yet: the expert term lives in the A2C "
+                                 "loss-gradient launch")
+        # optimizer: "rmsprop" (the reference's) or "adam" (torch's Adam, vn_adam_step_dev), with
+        # plain A2C or PPO, at any world
+        if optimizer not in ("rmsprop", "adam"):
+            raise ValueError("optimizer must be 'rmsprop' or 'adam', got %r" % (optimizer,))
+        self.optimizer = optimizer
+        self.adam_betas = (float(adam_betas[0]), float(adam_betas[1]))
+        self.adam_epsilon = float(adam_epsilon)
         if allreduce_buckets not in (1, 2):
             raise ValueError("allreduce_buckets must be 1 or 2")
         self.allreduce_buckets = int(allreduce_buckets)
@@ -116,6 +152,10 @@ class A2CTrainer:
         kw = dict(device=self.device)
         self.grads = torch.zeros(P, dtype=torch.float32, **kw)
         self.square_avg = torch.zeros(P, dtype=torch.float32, **kw)
+        if self.optimizer == "adam":
+            self.exp_avg = torch.zeros(P, dtype=torch.float32, **kw)
+            self.exp_avg_sq = torch.zeros(P, dtype=torch.float32, **kw)
+            self.adam_step = torch.zeros(1, dtype=torch.int64, **kw)  # updates taken, read on the device
         self.acts = self.net.new_acts(N)
         self.boot_acts = self.net.new_acts(E)
         self.out = torch.zeros((N, OUT_LD), dtype=torch.float32, **kw)
@@ -129,6 +169,12 @@ class A2CTrainer:
         self.returns = torch.zeros(N, dtype=torch.float32, **kw)
         self.dout = torch.zeros((N, OUT_LD), dtype=torch.float32, **kw)
         self.stats = torch.zeros(4, dtype=torch.float32, **kw)
+        if self.ppo:
+            # the behaviour policy's head outputs, fixed for the update; [mean, rstd] of its
+            # advantages; the last epoch's [kl sum, clipped samples, ratio sum, value-clipped samples]
+            self.out_old = torch.zeros((N, OUT_LD), dtype=torch.float32, **kw)
+            self.adv_stats = torch.zeros(2, dtype=torch.float32, **kw)
+            self.ppo_stats = torch.zeros(4, dtype=torch.float32, **kw)
         self.norm_partial = torch.zeros(512, dtype=torch.float64, **kw)
         self.scalars = torch.zeros(2, dtype=torch.float32, **kw)
         self.episode_stats = torch.zeros(3, dtype=torch.float32, **kw)  # count, return sum, length sum
@@ -253,8 +299,8 @@ class A2CTrainer:
             self.novelty_steps = torch.zeros(1, dtype=torch.int64, **kw)
             self.visit_seen = torch.zeros(2, dtype=torch.int64, **kw)  # [states seen, visits] of this rank
         self._metric_layout = metric_layout(bool(unreal), self.nav_metrics, self.expert, self.geo_curriculum is not None,
-                                            self.shaping, self.rp_skewed,
-                                            self.novelty)  # step()'s vector: {segment: (offset, width)}
+                                            self.shaping, self.rp_skewed, self.novelty,
+                                            ppo=self.ppo)  # step()'s vector: {segment: (offset, width)}
         self.workspace = torch.empty(self.net.workspace_floats(N), dtype=torch.float32, **kw)
         if self.recurrent:
             X = self.net.lstm["xcat"]
@@ -270,6 +316,8 @@ class A2CTrainer:
             self.masks = torch.ones((T, E), **f32)
             self.lra = torch.zeros((T, E, A1), **f32)
             self._hc0 = torch.zeros((2, E, 512), **f32)  # state entering the rollout
+            if self.ppo:  # the rollout's last (h, c), saved before an epoch's re-forward overwrites them
+                self._hc_last = torch.zeros((2, E, 512), **f32)
             self.h0, self.c0 = self._hc0[0], self._hc0[1]
             self.prev_action = torch.zeros(E, dtype=torch.int64, **kw)
             self.prev_reward = torch.zeros(E, **f32)
@@ -340,6 +388,9 @@ class A2CTrainer:
         if self.replay:
             self._replay_segs = self._replay_segments()
         self._custom_aux = type(self).compute_auxiliary_loss is not A2CTrainer.compute_auxiliary_loss
+        if self._custom_aux and self.ppo:
+            raise ValueError("ppo_clip does not run with a compute_auxiliary_loss override yet: its autograd pass "
+                             "is not repeated per epoch")
         if self._custom_aux and cuda_graph:
             raise ValueError("a compute_auxiliary_loss override runs torch autograd per update: use cuda_graph=False")
         self.aux_losses = {}
@@ -394,6 +445,7 @@ class A2CTrainer:
         self.num_updates = 0
         self.total_steps = 0
         self.cuda_graph = bool(cuda_graph)
+        self.on_ppo_epoch = None
         if self.cuda_graph and self.world > 1:
             if not vdist.capturable(process_group):
                 raise ValueError("cuda_graph=True at world > 1 needs the nccl (RCCL) backend: a gloo all-reduce "
@@ -967,7 +1019,10 @@ class A2CTrainer:
     def update(self, batch=None):
         """One A2C update on the rollout just sampled (``batch`` from sample_training_batch;
         None = the trainer's own rollout buffers with the on-policy aux batch; with
-        unreal_source='replay' the rollout is then pushed into the ring and a sequence drawn)."""
+        unreal_source='replay' the rollout is then pushed into the ring and a sequence drawn). With
+        ppo_clip set: ppo_epochs epochs over the same rollout (_ppo_update)."""
+        if self.ppo:
+            return self._ppo_update()
         lib, net = self.lib, self.net
         E, T, A = self.env.num_envs, self.num_steps, self.A
         N = T * E
@@ -1093,11 +1148,123 @@ class A2CTrainer:
             _lib.check(lib.vn_grad_norm(_lib.ptr(self.grads), P, ctypes.c_float(scale),
                                         ctypes.c_float(self.max_gradient_norm), _lib.ptr(self.norm_partial),
                                         _lib.ptr(self.scalars), st), "vn_grad_norm")
+        if self.optimizer == "adam":
+            return self._adam_step(scale)
         # lr of this update from the device schedule (== current_lr() of the host counters)
         _lib.check(lib.vn_rmsprop_step_dev(_lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.square_avg), P,
                                            ctypes.c_float(scale), _lib.ptr(self.scalars), _lib.ptr(self.lr_dev),
                                            ctypes.c_float(self.rms_alpha), ctypes.c_float(self.rms_epsilon), st),
                    "vn_rmsprop_step_dev")
+
+    def _adam_step(self, scale):
+        """torch's Adam on the clipped gradient, lr from the device schedule and the step count from
+        the device (vn_adam_step_dev): nothing of the host enters, so a captured update stays valid."""
+        P, c_float = _lib.ptr, ctypes.c_float
+        _lib.check(self.lib.vn_adam_step_dev(P(self.params), P(self.grads), P(self.exp_avg), P(self.exp_avg_sq),
+                                             self.net.n_params, c_float(scale), P(self.scalars), P(self.lr_dev),
+                                             P(self.adam_step), c_float(self.adam_betas[0]),
+                                             c_float(self.adam_betas[1]), c_float(self.adam_epsilon), self._stream()),
+                   "vn_adam_step_dev")
+
+    @property
+    def on_ppo_epoch(self):
+        """None, or a callable(k) run after epoch k's optimiser step of a PPO update (eager mode
+        only: a captured update has no host code between its launches)."""
+        return self._on_ppo_epoch
+
+    @on_ppo_epoch.setter
+    def on_ppo_epoch(self, fn):
+        if fn is not None and self.cuda_graph:
+            raise ValueError("on_ppo_epoch runs host code between the epochs, which a captured hipGraph cannot "
+                             "replay: use cuda_graph=False")
+        self._on_ppo_epoch = fn
+
+    def _ppo_reforward(self, goals):
+        """The stored rollout under the current parameters, into the rollout's own activation
+        buffers and self.out: one trunk call over all N rows, recurrent the T LSTM steps from the
+        (h0, c0) the rollout started from with its stored inputs and masks, then the heads."""
+        net, E, T = self.net, self.env.num_envs, self.num_steps
+        N = T * E
+        frames = self._frames(self.rows_img, self.rows_goal)
+        if not self.recurrent:
+            net.forward(self.params, frames, N, self.acts, N, 0, self.out, goals=goals)
+            return
+        net.forward(self.params, frames, N, self.acts, N, 0, None, goals=goals)
+        x5 = net.x5(self.acts, N)
+        for t in range(T):
+            sl = slice(t * E, (t + 1) * E)
+            hp = self.h0 if t == 0 else self.h_all[(t - 1) * E:t * E]
+            cp = self.c0 if t == 0 else self.c_all[(t - 1) * E:t * E]
+            net.lstm_step(self.params, E, x5[sl], self.lra[t], self.masks[t], hp, cp, self.xcat[sl], self.gates,
+                          self.lstm_acts[sl], self.c_all[sl], self.h_all[sl])
+        net.heads(self.params, self.h_all, N, self.out)
+
+    def _ppo_update(self):
+        """ppo_epochs full-batch epochs of the clipped surrogate on the rollout just sampled
+        (DESIGN.md "PPO epochs"). The returns, the behaviour policy's head outputs (out_old) and
+        the advantage statistics are formed once and stay fixed. Epoch 0 runs on the rollout's own
+        stored activations, as the A2C update does; every later epoch first re-forwards the stored
+        rollout under the current parameters (the backward consumes activations). After the
+        loss-gradient launch each epoch is the A2C chain: aux heads, LSTM and trunk backward,
+        norm, optimiser step. The carried (h, c) is the behaviour policy's: saved before the first
+        re-forward, written into (h0, c0) after the last epoch, so c0 is the rollout's start state
+        for every epoch's LSTM backward. No host value enters: the K epochs are captured in the
+        update's one hipGraph."""
+        lib, net, P, c_float = self.lib, self.net, _lib.ptr, ctypes.c_float
+        E, T, A = self.env.num_envs, self.num_steps, self.A
+        N = T * E
+        st = self._stream()
+        self._returns(self._novelty_rewards() if self.novelty else self.rewards, self.dones, self.boot_out, self.out,
+                      T, E, self.returns)
+        self.out_old.copy_(self.out)
+        if self.ppo_normalize_advantage:
+            _lib.check(lib.vn_ppo_adv_stats(P(self.returns), P(self.out_old), N, A, c_float(_PPO_ADV_EPS), P(self.adv_stats),
+                                            st), "vn_ppo_adv_stats")
+        if self.recurrent:
+            self._hc_last.copy_(self._hc_all.view(2, T, E, 512)[:, T - 1])
+        frames = self._frames(self.rows_img, self.rows_goal)
+        goals = None
+        if self.dedup_goals:  # the rollout's goal runs, for every epoch's re-forward and backward alike
+            _lib.check(lib.vn_goal_runs_rollout(P(self.dones), T, E, P(self.goal_list), P(self.goal_run_length),
+                                                P(self.goal_count[T:T + 1]), st), "vn_goal_runs_rollout")
+            goals = self._goal_runs_update
+        for k in range(self.ppo_epochs):
+            if k > 0:
+                self._ppo_reforward(goals)
+            _lib.check(lib.vn_ppo_loss_grad(
+                P(self.out), P(self.out_old), P(self.actions), P(self.returns),
+                P(self.adv_stats) if self.ppo_normalize_advantage else None, N, A, c_float(self.ppo_clip),
+                c_float(self.ppo_value_clip), c_float(self.value_coefficient), c_float(self.entropy_coefficient),
+                P(self.dout), P(self.stats), P(self.ppo_stats), st), "vn_ppo_loss_grad")
+            dx4 = None
+            if self.aux_weight > 0:  # the deconv heads on the rollout batch, as the A2C update runs them
+                self.aux_stats.zero_()
+                net.aux_forward_loss_grad(self.params, self.acts, N, N, self.a1, self.pred, self._aux_targets,
+                                          self.aux_weight, self.dpred, self.aux_stats, self.aux_ws)
+                net.aux_backward(self.params, self.acts, N, N, self.a1, self.dpred, self.grads, self.dx4, self.aux_ws)
+                dx4 = self.dx4
+            if self.recurrent:
+                net.lstm_backward(self.params, T, E, self.dout, self.h_all, self.xcat, self.lstm_acts, self.c_all,
+                                  self.c0, self.masks, net.x5(self.acts, N), self.dz5, self.grads, self.lstm_ws,
+                                  dh_extra=None, extra_envs=0)
+                net.backward_ex(self.params, frames, N, self.acts, N, None, self.dz5, dx4, self.grads, self.workspace,
+                                goals=goals)
+            else:
+                net.backward_ex(self.params, frames, N, self.acts, N, self.dout, None, dx4, self.grads,
+                                self.workspace, goals=goals)
+            _lib.check(lib.vn_grad_norm(P(self.grads), net.n_params, c_float(1.0), c_float(self.max_gradient_norm),
+                                        P(self.norm_partial), P(self.scalars), st), "vn_grad_norm")
+            if self.optimizer == "adam":
+                self._adam_step(1.0)
+            else:
+                _lib.check(lib.vn_rmsprop_step_dev(P(self.params), P(self.grads), P(self.square_avg), net.n_params,
+                                                   c_float(1.0), P(self.scalars), P(self.lr_dev),
+                                                   c_float(self.rms_alpha), c_float(self.rms_epsilon), st),
+                           "vn_rmsprop_step_dev")
+            if self._on_ppo_epoch is not None:
+                self._on_ppo_epoch(k)
+        if self.recurrent:
+            self._hc0.copy_(self._hc_last)
 
     def _buckets_split(self):
         """Two gradient buckets when the head bucket is final before the trunk backward:
@@ -1205,6 +1372,8 @@ class A2CTrainer:
             "novelty": lambda: [rsum(self.novelty_stats[:2].to(f64 if self.shaping else torch.float32)),
                                 self.visit_seen[:1].to(f64 if self.shaping else torch.float32)],
         }
+        if self.ppo:  # the final epoch's sums (fp32 sums of at most N terms; the vector's width)
+            tails["ppo"] = lambda: [self.ppo_stats.to(f64 if self.shaping else torch.float32)]
         for name in list(layout)[1:]:
             parts = tails[name]()
             m = torch.cat([m.to(parts[0].dtype)] + parts)
@@ -1272,6 +1441,10 @@ class A2CTrainer:
             added, firsts, seen = seg["novelty"]
             novelty = {"novelty_bonus": added / (N * self.world), "first_visit_rate": firsts / (N * self.world),
                        "states_seen": seen}
+        ppo = {}
+        if self.ppo:  # the final epoch's means over the N samples
+            ppo = dict(zip(("approx_kl", "clip_fraction", "ratio_mean", "value_clip_fraction"),
+                           (x / N for x in seg["ppo"])))
         dt = time.perf_counter() - t0
         return {
             "step": self.total_steps, "updates": self.num_updates,
@@ -1291,6 +1464,7 @@ class A2CTrainer:
             **shaping,
             **rp,
             **novelty,
+            **ppo,
         }
 
     def run(self, log_every=10, logger=print):

@@ -61,11 +61,36 @@ def _without_env_table(tr, key):
         raise KeyError(key)
 
 
+_ADAM_STATE = ("exp_avg", "exp_avg_sq", "adam_step")
+
+
+def _adam_state(tr):
+    """Adam's moments and step count of an optimizer='adam' trainer ({} otherwise)."""
+    if getattr(tr, "optimizer", "rmsprop") != "adam":
+        return {}
+    return {k: getattr(tr, k).cpu() for k in _ADAM_STATE}
+
+
+def _load_adam_state(tr, sd):
+    """Adam's state from a checkpoint; one saved without it (an RMSprop run's) starts the moments
+    and the step count at zero, with a warning."""
+    if getattr(tr, "optimizer", "rmsprop") != "adam":
+        return
+    if all(k in sd for k in _ADAM_STATE):
+        for k in _ADAM_STATE:
+            getattr(tr, k).copy_(sd[k].to(tr.device))
+        return
+    warnings.warn("checkpoint holds no Adam state (saved with optimizer='rmsprop'): the moments and the step "
+                  "count start at zero")
+    for k in _ADAM_STATE:
+        getattr(tr, k).zero_()
+
+
 def state_dict(tr):
     sd = {"params": tr.params.detach().cpu(), "square_avg": tr.square_avg.cpu(),
           **{key: v.cpu() for key, v in env_state(tr).items()},
           "num_updates": tr.num_updates, "sched": tr.sched.cpu(),
-          "total_steps": tr.total_steps, "seed": tr.seed, "rank": tr.rank, "world": tr.world}
+          "total_steps": tr.total_steps, "seed": tr.seed, "rank": tr.rank, "world": tr.world, **_adam_state(tr)}
     if tr.recurrent:
         for k in tr._RECURRENT_STATE:
             sd[k] = getattr(tr, k).cpu()
@@ -83,7 +108,7 @@ def params_state_dict(tr):
     step counters (what a single-process ``test()`` needs after distributed training)."""
     return {"params": tr.params.detach().cpu(), "square_avg": tr.square_avg.cpu(),
             "num_updates": tr.num_updates, "total_steps": tr.total_steps, "sched": tr.sched.cpu(),
-            "seed": tr.seed, "world": tr.world, "params_only": True}
+            "seed": tr.seed, "world": tr.world, "params_only": True, **_adam_state(tr)}
 
 
 def load_params_state_dict(tr, sd):
@@ -95,6 +120,7 @@ def load_params_state_dict(tr, sd):
     tr.params.copy_(sd["params"].to(tr.device))
     if "square_avg" in sd:
         tr.square_avg.copy_(sd["square_avg"].to(tr.device))
+    _load_adam_state(tr, sd)
     tr.num_updates = int(sd.get("num_updates", tr.num_updates))
     tr.total_steps = int(sd.get("total_steps", tr.total_steps))
     if "sched" in sd:
@@ -112,6 +138,7 @@ def load_state_dict(tr, sd):
                          % (int(sd["rank"]), int(sd["world"]), tr.rank, tr.world))
     tr.params.copy_(sd["params"].to(tr.device))
     tr.square_avg.copy_(sd["square_avg"].to(tr.device))
+    _load_adam_state(tr, sd)
     restore_env_state(tr, sd, missing=_without_env_table)
     if tr.expert:  # the env's own mask buffer = the restored states' masks (the next rollout's slot 0)
         tr.env.refresh_nav_outputs()

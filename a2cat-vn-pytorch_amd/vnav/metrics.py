@@ -3,7 +3,7 @@ once: _update_metrics assembles the vector from it, step() decodes it by segment
 
 
 def metric_layout(unreal=False, nav_metrics=False, expert=False, geo_curriculum=False, shaping=False,
-                  rp_sampling=False, novelty=False):
+                  rp_sampling=False, novelty=False, ppo=False):
     """{segment: (offset, width)} of the vector under these trainer flags, in the vector's order
     (its width: the last segment's offset + width). fp64 with ``shaping``, whose distance sums
     are exact there, fp32 otherwise."""
@@ -21,6 +21,9 @@ def metric_layout(unreal=False, nav_metrics=False, expert=False, geo_curriculum=
         # the novelty bonus (vn_a2c_novelty_rewards' stats4 and vn_visit_stats): the sum of the
         # added terms, the rollout's first visits, this rank's states with a count > 0
         ("novelty", 3, novelty),
+        # the final PPO epoch (vn_ppo_loss_grad's ppo_stats4), sums over the N samples: the k3
+        # estimate of KL(old || new), samples with |r - 1| > clip, the ratio, value-clipped samples
+        ("ppo", 4, ppo),
     )
     layout, offset = {}, 0
     for name, width, on in segments:

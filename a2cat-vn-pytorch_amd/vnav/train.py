@@ -144,6 +144,14 @@ class Experiment:
     first_visit_weight = 0.0
     novelty_anneal_steps = 0
     visit_counts = False
+    # PPO epochs over the stored rollout (A2CTrainer ppo_clip / ppo_epochs / ppo_value_clip /
+    # ppo_normalize_advantage): clip None = off, the one A2C step per rollout; and the optimiser
+    # (A2CTrainer optimizer): "rmsprop" or "adam"
+    ppo_clip = None
+    ppo_epochs = 4
+    ppo_value_clip = 0.0
+    ppo_normalize_advantage = True
+    optimizer = "rmsprop"
 
     def __init__(self, env_kwargs=None, model_kwargs=None, save_dir=None, seed=0, device=None, logger=print,
                  **overrides):
@@ -188,7 +196,9 @@ class Experiment:
                           shaping_anneal_steps=self.shaping_anneal_steps, gae_lambda=self.gae_lambda,
                           rp_sampling=self.rp_sampling, rp_batch=self.rp_batch, rp_skew=self.rp_skew,
                           novelty_weight=self.novelty_weight, first_visit_weight=self.first_visit_weight,
-                          novelty_anneal_steps=self.novelty_anneal_steps)
+                          novelty_anneal_steps=self.novelty_anneal_steps, ppo_clip=self.ppo_clip,
+                          ppo_epochs=self.ppo_epochs, ppo_value_clip=self.ppo_value_clip,
+                          ppo_normalize_advantage=self.ppo_normalize_advantage, optimizer=self.optimizer)
 
     def _setup(self):
         if self.trainer is None:
@@ -579,7 +589,25 @@ def main(argv=None):
     p.add_argument("--visit-counts", action="store_true",
                    help="keep the per-state visit table on the device without a bonus; with --test, report the "
                         "states the evaluation covered")
+    p.add_argument("--ppo-clip", type=float, default=None, metavar="C",
+                   help="PPO: --ppo-epochs full-batch epochs of the surrogate clipped at 1 +- C over every rollout "
+                        "(default: one A2C step per rollout)")
+    p.add_argument("--ppo-epochs", type=int, default=None, metavar="K", help="--ppo-clip: epochs per rollout (default 4)")
+    p.add_argument("--ppo-value-clip", type=float, default=None, metavar="CV",
+                   help="--ppo-clip: clip the critic's move from its rollout value at CV (default 0: off)")
+    p.add_argument("--no-adv-norm", action="store_true",
+                   help="--ppo-clip: use the advantages as they are, not normalised over the rollout")
+    p.add_argument("--optimizer", default=None, choices=("adam", "rmsprop"),
+                   help="the optimiser of the update (default rmsprop, the reference's)")
     a = p.parse_args(argv)
+    if a.ppo_clip is None and (a.ppo_epochs is not None or a.ppo_value_clip is not None or a.no_adv_norm):
+        p.error("--ppo-epochs / --ppo-value-clip / --no-adv-norm need --ppo-clip")
+    if a.ppo_clip is not None and not a.ppo_clip > 0:
+        p.error("--ppo-clip must be > 0")
+    if a.ppo_epochs is not None and a.ppo_epochs < 1:
+        p.error("--ppo-epochs must be at least 1")
+    if a.ppo_value_clip is not None and a.ppo_value_clip < 0:
+        p.error("--ppo-value-clip must be >= 0")
     for flag, v in (("--novelty-weight", a.novelty_weight), ("--first-visit-weight", a.first_visit_weight),
                     ("--novelty-anneal", a.novelty_anneal)):
         if v is not None and v < 0:
@@ -646,6 +674,12 @@ def main(argv=None):
             over[key] = v
     if a.visit_counts:
         over["visit_counts"] = True
+    for key, v in (("ppo_clip", a.ppo_clip), ("ppo_epochs", a.ppo_epochs), ("ppo_value_clip", a.ppo_value_clip),
+                   ("optimizer", a.optimizer)):
+        if v is not None:
+            over[key] = v
+    if a.no_adv_norm:
+        over["ppo_normalize_advantage"] = False
     exp = make_trainer(a.name, env_kwargs=env_kwargs, save_dir=a.save_dir, seed=a.seed, **over)
     fixed = a.eval_episodes is not None or a.eval_set is not None
     if not fixed and (a.eval_buckets or a.greedy or a.save_eval_set or a.eval_max_steps is not None):

@@ -999,6 +999,51 @@ int vn_rmsprop_step_dev(float* params, const float* grads, float* square_avg, in
                         const float* scalars2, const float* lr_dev, float alpha, float eps,
                         vn_stream_t stream);
 
+/* PPO epochs over a stored rollout (DESIGN.md "PPO epochs", csrc/vn_ppo.hip). out / out_old /
+ * dout are [n][8] rows as in vn_a2c_loss_grad: logits in columns 0..A-1, the value in column A;
+ * out_old is the behaviour policy's copy of the rollout's out, fixed for the whole update.
+ *
+ * vn_ppo_adv_stats: stats2_dev [2] f32 on the device = [mean, 1 / (std + eps)] of
+ * adv_i = returns[i] - out_old[i][A], std the population standard deviation (divide by n; n == 1
+ * gives std = 0). One launch: fp64 sums in a fixed order, the mean first, then the squares centred
+ * on it, each result rounded once to fp32; no atomics, so the same input gives the same bits.
+ * VN_EINVAL, nothing written: a NULL buffer, n <= 0, num_actions outside 1..7, eps <= 0. */
+int vn_ppo_adv_stats(const float* returns, const float* out_old, int n, int num_actions, float eps,
+                     float* stats2_dev, vn_stream_t stream);
+/* The clipped-surrogate loss gradient of one epoch, one launch of vn_a2c_loss_grad's shape. With
+ * p, logp, H of out and logp_old of out_old as vn_a2c_loss_grad computes them, a the action,
+ * R = returns[i], V = out[i][A], V_old = out_old[i][A], c = clip, cv = value_clip:
+ *   d = logp_a - logp_old_a, r = expf(d);
+ *   adv = R - V_old; A^ = (adv - mean) rstd with [mean, rstd] = adv_stats2_dev read on the
+ *   device (vn_ppo_adv_stats' output), A^ = adv when adv_stats2_dev == NULL;
+ *   s1 = r A^, s2 = clamp(r, 1 - c, 1 + c) A^; the surrogate is min(s1, s2), and its gradient
+ *   flows where s1 <= s2 (a tie included): g = -A^ r there, else 0;
+ *   dout[i][j] = (g (ind_j - p_j) + ec p_j (logp_j + H)) / n for j < A;
+ *   value head, e1 = R - V: with cv <= 0, lv = e1^2 and dout[i][A] = vc (-2 e1) / n (the A2C
+ *   convention); else Vc = V_old + clamp(V - V_old, -cv, cv), e2 = R - Vc, lv = max(e1^2, e2^2)
+ *   and dout[i][A] is as above where e1^2 >= e2^2, else 0;
+ *   columns above A are 0.
+ * stats4 = sums of (lv, -min(s1, s2), H, R), the layout vn_a2c_metrics_ex reads. ppo_stats4 =
+ * sums of (expm1f(d) - d, [|r - 1| > c], r, [e2^2 > e1^2]): the first is the k3 estimate of
+ * KL(old || new), accurate near r = 1. Both are zeroed by the call. When out_old is out itself
+ * (neither is written) r is exactly 1 and the policy and value columns are vn_a2c_loss_grad's
+ * expression. VN_EINVAL, nothing written: a NULL buffer (adv_stats2_dev may be NULL), n <= 0,
+ * num_actions outside 1..7, clip <= 0. */
+int vn_ppo_loss_grad(const float* out, const float* out_old, const int32_t* actions, const float* returns,
+                     const float* adv_stats2_dev, int n, int num_actions, float clip, float value_clip,
+                     float value_coef, float entropy_coef, float* dout, float* stats4, float* ppo_stats4,
+                     vn_stream_t stream);
+/* torch's Adam without weight decay or amsgrad on the flat buffers, vn_rmsprop_step_dev's shape:
+ *   g = grads (scalars2[1] scale); m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g^2;
+ *   t = *step_dev + 1; bc1 = 1 - beta1^t and bc2 = 1 - beta2^t formed in fp64 on the device;
+ *   p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps), lr = *lr_dev.
+ * lr and t are read on the device, so a captured update stays valid. step_dev (int64) advances by
+ * one per call, in a launch of its own behind the step. VN_EINVAL, nothing written: a NULL
+ * buffer, n <= 0. */
+int vn_adam_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float scale,
+                     const float* scalars2, const float* lr_dev, int64_t* step_dev, float beta1, float beta2,
+                     float eps, vn_stream_t stream);
+
 /* Copy the message of the calling thread's last error (NUL-terminated). */
 int vn_last_error(char* buf, size_t len);
 const char* vn_version(void);

@@ -1,0 +1,155 @@
+"""What a PPO epoch costs beside the A2C update it repeats, Adam against RMSprop, and what K = 4
+epochs do on one small task.
+
+--mode cost (default), in one process, variants alternating, 5 rounds after a warm-up, one event
+pair around the timed updates: device time of A2CTrainer.step() (rollout + update) for
+  a2c        the trainer built without the new arguments (the parent commit's update, bit for bit)
+  ppo1/2/4   ppo_clip=0.2 with 1, 2 and 4 epochs (RMSprop)
+  a2c_adam   the A2C update with optimizer="adam"
+at
+  envs4096_84_lstm    4096 envs, 84x84, LSTM, eager
+  envs4_174_graph     4 envs, 174x174, LSTM, captured hipGraph
+and from the medians: ppo1 - a2c (the loss-gradient launch, the copy of out and the advantage
+statistics), the cost of one extra epoch ((ppo4 - ppo1) / 3 and ppo2 - ppo1), and that cost as a
+share of the A2C step.
+
+--mode learn: the expert test's setting (one 6x6 scene with one goal, 16 envs x 20 steps, 120
+updates, feed-forward 84x84, limit 30, the seeds of shaping_bench / visit_bench): success rate of
+the finished episodes over the last 20 updates and their number, A2C against PPO K = 4 (RMSprop at
+the same learning rate, and Adam), 3 seeds each.
+
+Writes <out>/ppo_bench.json or <out>/ppo_learn.json and prints the same JSON line.
+
+    python tools/ppo_bench.py [--mode cost|learn] [--rounds 5] [--out DIR]
+"""
+import argparse
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "a2cat-vn-pytorch_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+SEED = 1000
+VARIANTS = {"a2c": {}, "ppo1": dict(ppo_clip=0.2, ppo_epochs=1), "ppo2": dict(ppo_clip=0.2, ppo_epochs=2),
+            "ppo4": dict(ppo_clip=0.2, ppo_epochs=4), "a2c_adam": dict(optimizer="adam")}
+
+
+def spread(xs):
+    xs = sorted(xs)
+    return {"min": xs[0], "median": float(np.median(xs)), "max": xs[-1], "runs": xs}
+
+
+def time_update(kw, scenes, E, graph, warmup, K, dev):
+    """Device milliseconds per A2CTrainer.step()."""
+    import vnav
+    env = vnav.VectorEnv(scenes, E, seed=SEED, device=dev)
+    tr = vnav.A2CTrainer(env, recurrent=True, cuda_graph=graph, seed=1, **kw)
+    for _ in range(warmup):
+        tr.step(sync=False)
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize(dev)
+    ev0.record()
+    for _ in range(K):
+        tr.step(sync=False)
+    ev1.record()
+    torch.cuda.synchronize(dev)
+    ms = ev0.elapsed_time(ev1) / K
+    env.close()
+    del tr, env
+    torch.cuda.empty_cache()
+    return ms
+
+
+def cost(a, dev):
+    import vnav
+    res = {"tool": "ppo_bench", "mode": "cost",
+           "config": {"seed": SEED, "rounds": a.rounds, "updates": a.updates, "update_warmup": a.update_warmup,
+                      "variants": VARIANTS},
+           "update": {"unit": "ms per A2CTrainer.step() (device, one event pair)"}}
+    points = (("envs4096_84_lstm", [vnav.synthetic_scene(k) for k in range(20)], 4096, False, 1),
+              ("envs4_174_graph", [vnav.synthetic_scene(0, frame_shape=(174, 174, 3))], 4, True, 10))
+    for name, sc, E, graph, mult in points:
+        ms = {v: [] for v in VARIANTS}
+        for _ in range(a.rounds):
+            for v, kw in VARIANTS.items():
+                ms[v].append(time_update(kw, sc, E, graph, a.update_warmup, a.updates * mult, dev))
+        sp = {v: spread(ms[v]) for v in VARIANTS}
+        med = {v: sp[v]["median"] for v in VARIANTS}
+        epoch = (med["ppo4"] - med["ppo1"]) / 3.0
+        res["update"][name] = dict(
+            sp, envs=E, frame=list(sc[0].frame_shape), cuda_graph=graph, updates_timed=a.updates * mult,
+            ppo1_minus_a2c_ms={"median": med["ppo1"] - med["a2c"],
+                               "by_round": [x - y for x, y in zip(ms["ppo1"], ms["a2c"])]},
+            extra_epoch_ms={"from_ppo4": epoch, "from_ppo2": med["ppo2"] - med["ppo1"]},
+            extra_epoch_share_of_a2c_step=epoch / med["a2c"],
+            adam_minus_rmsprop_ms={"median": med["a2c_adam"] - med["a2c"],
+                                   "by_round": [x - y for x, y in zip(ms["a2c_adam"], ms["a2c"])]})
+    return res, "ppo_bench.json"
+
+
+LEARN = {"a2c": {}, "ppo4": dict(ppo_clip=0.2, ppo_epochs=4),
+         "ppo4_adam": dict(ppo_clip=0.2, ppo_epochs=4, optimizer="adam")}
+
+
+def learn_run(kw, seed, updates, dev):
+    import vnav
+    scene, goal, limit = vnav.synthetic_scene(0, grid=6), 7, 30
+    env = vnav.VectorEnv([scene], 16, seed=seed + 1, device=dev, max_episode_steps=limit)
+    env.set_tasks([(0, goal)])
+    env.reset()
+    tr = vnav.A2CTrainer(env, num_steps=20, seed=seed, max_time_steps=1e6, nav_metrics=True, **kw)
+    ok = eps = 0.0
+    kl = clipped = None  # A2C reports neither
+    for u in range(updates):
+        m = tr.step()
+        n_ep, n_ok = (float(x) for x in tr.nav_stats[:2].cpu())
+        if u >= updates - 20:
+            eps += n_ep
+            ok += n_ok
+        kl, clipped = m.get("approx_kl", kl), m.get("clip_fraction", clipped)
+    env.close()
+    return ok / eps if eps else float("nan"), eps, kl, clipped
+
+
+def learn(a, dev):
+    res = {"tool": "ppo_bench", "mode": "learn",
+           "config": {"task": "synthetic_scene(0, grid=6), goal 7, limit 30", "envs": 16, "num_steps": 20,
+                      "updates": a.learn_updates, "seeds": [0, 1, 2], "variants": LEARN,
+                      "measure": "successes / finished episodes over the last 20 updates, and their number; "
+                                 "approx_kl and clip_fraction of the last update"},
+           "runs": {}}
+    for name, kw in LEARN.items():
+        rows = [learn_run(kw, seed, a.learn_updates, dev) for seed in (0, 1, 2)]
+        res["runs"][name] = {"success_rate": [r[0] for r in rows], "episodes": [r[1] for r in rows],
+                             "approx_kl": [r[2] for r in rows], "clip_fraction": [r[3] for r in rows]}
+    return res, "ppo_learn.json"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=("cost", "learn"), default="cost")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--updates", type=int, default=30)
+    ap.add_argument("--update-warmup", type=int, default=5)
+    ap.add_argument("--learn-updates", type=int, default=120)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ppo"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("ppo_bench needs the GPU (no CPU timing)")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    res, name = cost(a, dev) if a.mode == "cost" else learn(a, dev)
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, name), "w") as f:
+        f.write(json.dumps(res, indent=1) + "\n")
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
