@@ -22,8 +22,8 @@ Modules
   a2c_cases.py  deterministic inputs of the A2C step tests (shared by the GPU tests and
               the CPU check of their draws' distance to the CDF boundaries)
   trunk_checks.py  the checks the GPU policy tests share: error measures, the activation
-              store's views and ReLU masks, gradients vs the fp64 oracle, the recurrent core
-              vs torch's float64 nn.LSTM
+              store's views and ReLU masks (under goal runs read at each run's start), gradients vs
+              the fp64 oracle, the recurrent core vs torch's float64 nn.LSTM
   few_env_cases.py  case tables and inputs of the few-env / float-frame / 1..7-action tests
   unreal_head_cases.py  case tables of the UNREAL head tests and the launch rules (split-K,
               weight-gradient slabs, reduce lanes, colsum blocks) that place them
@@ -33,5 +33,9 @@ Modules
   goal_trunk_cases.py  the goal trunk's launch regimes above 16 rows at the three geometries (the
               split-K / slab / lane rules of unreal_head_cases.py on its shapes, the persistent kernels'
               band structs restated), the switches in n and a smallest case list around them
+  lstm_regime_cases.py  the recurrent core's launch regimes from 18 to 1030 envs (the same split-K / slab /
+              lane rules on the shapes of gates, dh, dz5, dW_cat and the heads), the switches in E found
+              from the launch code's inequalities, a case list covering every value of every key, the
+              calling forms above 16 envs, and inputs made on the CPU (lstm_core_check(inputs=...))
   update_checks.py  one A2CTrainer update restated in float64, the UNREAL terms included
 """

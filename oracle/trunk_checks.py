@@ -8,7 +8,9 @@ masks of the GPU forward (the oracle is run with them, see GoalNetOracle.forward
 every disagreeing bit is asserted to be a tie), the comparison of the 14 (+ aux) parameter
 gradients, the whole forward + backward of the goal trunk on u8 frames (trunk_heads_u8_vs_oracle,
 which tests/test_goal_trunk_regimes_gpu.py runs at every launch regime above 16 rows), and the
-recurrent core against torch's float64 nn.LSTM (lstm_core_check). The
+recurrent core against torch's float64 nn.LSTM (lstm_core_check, which
+tests/test_lstm_regimes_gpu.py runs at every launch regime from 18 to 1030 envs on inputs made
+on the CPU). The
 BigHouse trunk's twins (_bighouse_masks, _bighouse_forward_masked, _ties_only,
 _bighouse_grads_vs_oracle) serve tests/test_bighouse_regimes_gpu.py and oracle/update_checks.py.
 
@@ -77,22 +79,38 @@ def _acts_views(net, acts, n):
     return out
 
 
-def _gpu_masks(net, acts, n, float_frames=False):
+def _gpu_masks(net, acts, n, float_frames=False, goal_src=None):
     """0/1 float64 masks (NCHW) of every trunk ReLU from the GPU's activations; checks that
     conv1's channel bitmask (what conv2's input gradient reads) equals X1 > 0. float_frames:
     the forward ran on dense float frames, whose conv1 (the im2col product) writes no bitmask
     (the conv2 input gradient of that path reads X1 itself), so the mask is X1 > 0 alone. Read
-    the masks before the backward runs: it overwrites X1."""
+    the masks before the backward runs: it overwrites X1. goal_src: int64 [n], the forward ran
+    with goal runs (vn_goal_runs): sample i's goal maps are those stored at sample goal_src[i]
+    (the start of its run, i + goal_delta[i]), the goal slots of the other samples are not
+    written; the goal masks are read there and the bitmask is checked on the image slots and
+    on the run starts' goal slots."""
     v = _acts_views(net, acts, n)
     x1 = v["X1"] > 0
+    x2g = v["X2"][:, 1] > 0
+    if goal_src is not None:
+        goal_src = goal_src.to(acts.device)
     if not float_frames:
-        bits = (v["M1"][..., None] >> torch.arange(32, device=acts.device, dtype=torch.int32)) & 1
-        assert torch.equal(bits.bool(), x1), "conv1 ReLU bitmask != X1 > 0"
+        bits = ((v["M1"][..., None] >> torch.arange(32, device=acts.device, dtype=torch.int32)) & 1).bool()
+        if goal_src is None:
+            assert torch.equal(bits, x1), "conv1 ReLU bitmask != X1 > 0"
+        else:
+            start = goal_src == torch.arange(n, device=acts.device)
+            assert bool(start.any()) and bool(start[goal_src].all()) and int(goal_src.min()) >= 0
+            assert torch.equal(bits[:, 0], x1[:, 0]), "conv1 ReLU bitmask != X1 > 0 (image frames)"
+            assert torch.equal(bits[start, 1], x1[start, 1]), "conv1 ReLU bitmask != X1 > 0 (goal frames of run starts)"
+    x1g = x1[:, 1]
+    if goal_src is not None:
+        x1g, x2g = x1g[goal_src], x2g[goal_src]
 
     def nchw(t):
         return t.permute(0, 3, 1, 2).double().cpu()
-    return {"m1i": nchw(x1[:, 0]), "m1g": nchw(x1[:, 1]), "m2i": nchw(v["X2"][:, 0] > 0),
-            "m2g": nchw(v["X2"][:, 1] > 0), "m3": nchw(v["X3"] > 0), "m4": nchw(v["X4"] > 0),
+    return {"m1i": nchw(x1[:, 0]), "m1g": nchw(x1g), "m2i": nchw(v["X2"][:, 0] > 0),
+            "m2g": nchw(x2g), "m3": nchw(v["X3"] > 0), "m4": nchw(v["X4"] > 0),
             "m5": (v["X5"] > 0).double().cpu()}
 
 
@@ -283,7 +301,7 @@ def roundup4(x):
     return (x + 3) // 4 * 4
 
 
-def lstm_core_check(E, T=3, A=4, masks=None, null_args=False, dh_extra=0, strict=False):
+def lstm_core_check(E, T=3, A=4, masks=None, null_args=False, dh_extra=0, strict=False, inputs=None, nan_fill=False):
     """The recurrent core of E envs x T steps through vn_lstm_forward_step, vn_policy_heads and
     vn_lstm_backward against torch's float64 nn.LSTM with the restated MaskedRNN convention:
     (h, c) of all steps, the heads on h and the gradients of W_ih, W_hh, both biases and both
@@ -295,7 +313,15 @@ def lstm_core_check(E, T=3, A=4, masks=None, null_args=False, dh_extra=0, strict
     of the first S envs; the reference loss gains sum(h[:, :S] * dh_extra). strict adds the
     checks of tests/test_few_env_gpu.py: the layout numbers of vn_policy_lstm_info, the stored
     xcat rows bitwise against [x5 | lra | 0 | m h_prev] built on the host side, (h, c) of every
-    step against that step's own scale. Returns the errors by name."""
+    step against that step's own scale. Returns the errors by name.
+
+    inputs: a dict of numpy arrays made on the CPU (oracle/lstm_regime_cases.py inputs(): x5 [T E, 512],
+    lra [T, E, A + 1], masks [T, E], h0, c0 [E, 512], actions int32 [T E], rets [T E], dh_extra
+    [T, S, 512] or None) in place of the tensors drawn here; masks must then be None. nan_fill: every
+    buffer the calls write (xcat, gates, acts, c_all, h_all, out, dz5, the workspace and grads) is
+    prefilled with NAN_BITS; after the backward no NaN may remain in dz5 or in the heads' and the LSTM's
+    gradients, W_cat's pad columns must be exactly zero, and the trunk's part of grads must still hold
+    the fill (include/vnav.h: the call writes the head and LSTM gradients)."""
     from vnav.policy import PolicyNet
     net = PolicyNet((84, 84), A, recurrent=True)
     params = net.init_params(3)
@@ -306,17 +332,28 @@ def lstm_core_check(E, T=3, A=4, masks=None, null_args=False, dh_extra=0, strict
     if strict:
         assert L["lin"] == 512 + A + 1 and L["xoff"] == roundup4(512 + A + 1) and L["xcat"] == L["xoff"] + 512, L
     g = torch.Generator(device="cuda").manual_seed(4)
-    x5 = torch.relu(torch.randn((N, 512), device="cuda", generator=g))
-    lra = torch.zeros((T, E, A + 1), device="cuda")
-    lra[..., :A].scatter_(2, torch.randint(0, A, (T, E, 1), device="cuda", generator=g), 1.0)
-    lra[..., A] = (torch.rand((T, E), device="cuda", generator=g) < 0.1).float()
-    if masks is None:
-        masks = (torch.rand((T, E), device="cuda", generator=g) > 0.05).float()
+    if inputs is not None:
+        assert masks is None and (inputs["dh_extra"] is not None) == bool(dh_extra)
+
+        def given(name, shape, dtype=torch.float32):
+            t = torch.as_tensor(np.ascontiguousarray(inputs[name]))
+            assert t.dtype == dtype and tuple(t.shape) == shape, (name, t.dtype, tuple(t.shape))
+            return t.cuda()
+        x5, lra, masks = given("x5", (N, 512)), given("lra", (T, E, A + 1)), given("masks", (T, E))
+        h0, c0 = given("h0", (E, 512)), given("c0", (E, 512))
+        assert torch.equal(lra, lra * masks[..., None])  # a reset env's last action / reward is zero, as below
     else:
-        masks = torch.as_tensor(np.asarray(masks), dtype=torch.float32).cuda().reshape(T, E).contiguous()
-    lra *= masks[..., None]
-    h0 = torch.randn((E, 512), device="cuda", generator=g) * 0.5
-    c0 = torch.randn((E, 512), device="cuda", generator=g) * 0.5
+        x5 = torch.relu(torch.randn((N, 512), device="cuda", generator=g))
+        lra = torch.zeros((T, E, A + 1), device="cuda")
+        lra[..., :A].scatter_(2, torch.randint(0, A, (T, E, 1), device="cuda", generator=g), 1.0)
+        lra[..., A] = (torch.rand((T, E), device="cuda", generator=g) < 0.1).float()
+        if masks is None:
+            masks = (torch.rand((T, E), device="cuda", generator=g) > 0.05).float()
+        else:
+            masks = torch.as_tensor(np.asarray(masks), dtype=torch.float32).cuda().reshape(T, E).contiguous()
+        lra *= masks[..., None]
+        h0 = torch.randn((E, 512), device="cuda", generator=g) * 0.5
+        c0 = torch.randn((E, 512), device="cuda", generator=g) * 0.5
     if null_args:
         lra.zero_()
         masks.fill_(1.0)
@@ -328,6 +365,9 @@ def lstm_core_check(E, T=3, A=4, masks=None, null_args=False, dh_extra=0, strict
     h_all = torch.zeros((N, 512), device="cuda")
     gates = torch.zeros((E, 2048), device="cuda")
     out = torch.zeros((N, 8), device="cuda")
+    if nan_fill:
+        for buf in (xcat, la, c_all, h_all, gates, out):
+            buf.view(torch.int32).fill_(NAN_BITS)
     for t in range(T):
         sl = slice(t * E, (t + 1) * E)
         hp = h0 if t == 0 else h_all[(t - 1) * E:t * E]
@@ -345,19 +385,41 @@ def lstm_core_check(E, T=3, A=4, masks=None, null_args=False, dh_extra=0, strict
             want = torch.cat((x5[sl], lra[t], torch.zeros((E, L["xoff"] - L["lin"]), device="cuda"),
                               hp * masks[t][:, None]), 1)
             assert torch.equal(xcat[sl].view(torch.int32), want.view(torch.int32)), "xcat rows of step %d" % t
-    actions = torch.randint(0, A, (N,), dtype=torch.int32, device="cuda", generator=g)
-    rets = torch.randn(N, device="cuda", generator=g)
+    if inputs is not None:
+        actions, rets = given("actions", (N,), torch.int32), given("rets", (N,))
+    else:
+        actions = torch.randint(0, A, (N,), dtype=torch.int32, device="cuda", generator=g)
+        rets = torch.randn(N, device="cuda", generator=g)
     dout = a2c_loss_grad(out, actions, rets, A)
     grads = torch.zeros_like(params)
     dz5 = torch.zeros((N, 512), device="cuda")
     ws = torch.empty(net.lstm_workspace_floats(T, E), device="cuda")
+    if nan_fill:
+        for buf in (grads, dz5, ws):
+            buf.view(torch.int32).fill_(NAN_BITS)
     dhx = None
-    if dh_extra:
+    if dh_extra and inputs is not None:
+        dhx = given("dh_extra", (T, dh_extra, 512))
+    elif dh_extra:
         gx = torch.Generator(device="cuda").manual_seed(6)
         dhx = torch.randn((T, dh_extra, 512), device="cuda", generator=gx) * 0.1
     net.lstm_backward(params, T, E, dout, h_all, xcat, la, c_all, c0, masks, x5, dz5, grads, ws, dh_extra=dhx,
                       extra_envs=dh_extra)
     torch.cuda.synchronize()
+    if nan_fill:
+        gv = net.views(grads)
+        assert not bool(torch.isnan(dz5).any()), "dz5: rows left unwritten"
+        wcat_g, bih_g, bhh_g = gv["lstm"]
+        for name, t in (("W_cat", wcat_g), ("b_ih", bih_g), ("b_hh", bhh_g), ("head weight", gv["head"][0]),
+                        ("head bias", gv["head"][1])):
+            assert not bool(torch.isnan(t).any()), "%s gradient: values left unwritten" % name
+        pad = wcat_g[:, L["lin"]:L["xoff"]]
+        assert not bool(pad.any()), "W_cat gradient: pad columns %d..%d not zero" % (L["lin"], L["xoff"] - 1)
+        for name in net.offsets:
+            if name == "head":
+                continue
+            for t in gv[name]:
+                assert bool((t.contiguous().view(torch.int32) == NAN_BITS).all()), "%s gradient written by vn_lstm_backward" % name
 
     sd = net.to_reference(params)
     lstm = torch.nn.LSTM(512 + A + 1, 512, batch_first=True).double()
@@ -405,7 +467,7 @@ def lstm_core_check(E, T=3, A=4, masks=None, null_args=False, dh_extra=0, strict
     for mod, k in ((pl, "policy_logits.0"), (cr, "critic.0")):
         gerrs[k + ".weight"] = _err(mine[k + ".weight"].numpy(), mod.weight.grad.numpy())
         gerrs[k + ".bias"] = _err(mine[k + ".bias"].numpy(), mod.bias.grad.numpy())
-    bad = {k: "%.3g" % e for k, e in gerrs.items() if e > 1e-4}
+    bad = {k: "%.3g" % e for k, e in gerrs.items() if not e <= 1e-4}  # a NaN error fails too
     assert not bad, bad
     print("LSTM E=%d T=%d A=%d: worst gradient error %.3g of scale" % (E, T, A, max(gerrs.values())))
     errs.update(gerrs)

@@ -19,8 +19,12 @@ on its own, so the gradient with one term dropped is the total minus that term's
 gives, per UNREAL term, its share of a tensor it has in common with the A2C loss, in units of
 that tensor's scale in the total — a term below the tolerance could go missing unnoticed.
 
-Used by tests/test_prod_oracle_gpu.py (the logged run's shape, no UNREAL) and
-tests/test_unreal_update_gpu.py.
+Above 16 envs the goal net's trainer runs shared_base on a goal frame once per goal run
+(vn_goal_runs); the restatement runs it on every sample and takes a sample's goal-map masks
+from the start of its run, where the GPU stored them.
+
+Used by tests/test_prod_oracle_gpu.py (the logged run's shape, no UNREAL),
+tests/test_unreal_update_gpu.py and tests/test_lstm_regimes_gpu.py (20 and 136 envs).
 """
 import dataclasses
 
@@ -117,7 +121,14 @@ def second_update_vs_fp64(scene, graph, spd, frames, E, T, seed, env_seed, max_s
     if arch == "bighouse":
         masks, bmasks = _bighouse_masks(net, tr.acts, N), _bighouse_masks(net, tr.boot_acts, E)
     else:
-        masks, bmasks = _gpu_masks(net, tr.acts, N), _gpu_masks(net, tr.boot_acts, E)
+        # above 16 envs the trainer runs shared_base on a goal frame once per goal run (vn_goal_runs): a
+        # sample's goal maps, and so their ReLU masks, are those stored at the start of its run
+        src = None
+        if tr.dedup_goals:
+            src = torch.arange(N) + tr.goal_delta.cpu().view(-1).long()
+            starts = torch.cat((torch.ones(1, E, dtype=torch.bool), tr.dones.cpu().view(T, E)[:-1].bool())).view(-1)
+            assert torch.equal(src == torch.arange(N), starts), "goal runs start at step 0 and after each done"
+        masks, bmasks = _gpu_masks(net, tr.acts, N, goal_src=src), _gpu_masks(net, tr.boot_acts, E)
     amasks = None
     if w > 0:  # the aux heads' ReLU masks: the same first layer run on the rollout's X4
         a1buf, predbuf = net.aux_buffers(N)
