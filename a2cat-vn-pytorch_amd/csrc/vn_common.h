@@ -34,6 +34,7 @@ enum : uint32_t {
   STREAM_REPLAY = 4,  // the replay ring's slot draw (vn_replay_push_draw)
   STREAM_EPISODES = 5,  // the evaluation episode draw (vn_nav_sample_episodes)
   STREAM_RP = 6,      // the reward-skewed reward-prediction draw (vn_unreal_rp_sample)
+  STREAM_PPO = 7,     // the PPO epoch's env permutation keys (vn_ppo_env_permutation)
 };
 
 __host__ __device__ inline void mulhilo32(uint32_t a, uint32_t b, uint32_t& hi, uint32_t& lo) {

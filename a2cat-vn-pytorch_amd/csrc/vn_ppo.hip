@@ -196,21 +196,40 @@ int vn_ppo_adv_stats(const float* returns, const float* out_old, int n, int num_
   return VN_OK;
 }
 
-int vn_ppo_loss_grad(const float* out, const float* out_old, const int32_t* actions, const float* returns,
-                     const float* adv_stats2_dev, int n, int num_actions, float clip, float value_clip,
-                     float value_coef, float entropy_coef, float* dout, float* stats4, float* ppo_stats4,
-                     vn_stream_t stream) {
+// The loss-gradient launch behind both entries: `clear` zeroes the two sum vectors first.
+static int ppo_loss_grad_launch(const char* who, bool clear, const float* out, const float* out_old,
+                                const int32_t* actions, const float* returns, const float* adv_stats2_dev, int n,
+                                int num_actions, float clip, float value_clip, float value_coef, float entropy_coef,
+                                float* dout, float* stats4, float* ppo_stats4, vn_stream_t stream) {
   if (!out || !out_old || !actions || !returns || !dout || !stats4 || !ppo_stats4 || n <= 0 || num_actions < 1 ||
       num_actions > 7 || !(clip > 0.0f))
-    return fail(VN_EINVAL, "vn_ppo_loss_grad: bad args");
+    return fail(VN_EINVAL, std::string(who) + ": bad args");
   hipStream_t st = (hipStream_t)stream;
-  VN_HIP(hipMemsetAsync(stats4, 0, 4 * sizeof(float), st));
-  VN_HIP(hipMemsetAsync(ppo_stats4, 0, 4 * sizeof(float), st));
+  if (clear) {
+    VN_HIP(hipMemsetAsync(stats4, 0, 4 * sizeof(float), st));
+    VN_HIP(hipMemsetAsync(ppo_stats4, 0, 4 * sizeof(float), st));
+  }
   hipLaunchKernelGGL(ppo_loss_grad_kernel, dim3((n + 255) / 256), dim3(256), 0, st, out, out_old, actions, returns,
                      adv_stats2_dev, n, num_actions, clip, value_clip, value_coef, entropy_coef, 1.0f / (float)n, dout,
                      stats4, ppo_stats4);
   VN_HIP(hipGetLastError());
   return VN_OK;
+}
+
+int vn_ppo_loss_grad(const float* out, const float* out_old, const int32_t* actions, const float* returns,
+                     const float* adv_stats2_dev, int n, int num_actions, float clip, float value_clip,
+                     float value_coef, float entropy_coef, float* dout, float* stats4, float* ppo_stats4,
+                     vn_stream_t stream) {
+  return ppo_loss_grad_launch("vn_ppo_loss_grad", true, out, out_old, actions, returns, adv_stats2_dev, n, num_actions,
+                              clip, value_clip, value_coef, entropy_coef, dout, stats4, ppo_stats4, stream);
+}
+
+int vn_ppo_loss_grad_acc(const float* out, const float* out_old, const int32_t* actions, const float* returns,
+                         const float* adv_stats2_dev, int n, int num_actions, float clip, float value_clip,
+                         float value_coef, float entropy_coef, float* dout, float* stats4, float* ppo_stats4,
+                         vn_stream_t stream) {
+  return ppo_loss_grad_launch("vn_ppo_loss_grad_acc", false, out, out_old, actions, returns, adv_stats2_dev, n,
+                              num_actions, clip, value_clip, value_coef, entropy_coef, dout, stats4, ppo_stats4, stream);
 }
 
 int vn_adam_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float scale,

@@ -120,6 +120,15 @@ class RpRing(ctypes.Structure):
     ]
 
 
+PPO_PERM_TILE = 1024  # VN_PPO_PERM_TILE: keys vn_ppo_env_permutation stages in LDS per pass
+
+
+class PpoRollout(ctypes.Structure):
+    """vn_ppo_rollout (include/vnav.h)."""
+    _fields_ = [(name, c_void_p) for name in ("rows_img", "rows_goal", "actions", "returns", "out_old", "dones",
+                                              "masks", "lra", "h0", "c0", "goal_delta")]
+
+
 class EpisodeLog(ctypes.Structure):
     """vn_episode_log (include/vnav.h)."""
     _fields_ = [
@@ -319,6 +328,11 @@ SIGNATURES.update({
                                  c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vn_adam_step_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p,
                                  c_void_p, c_float, c_float, c_float, c_void_p]),
+    "vn_ppo_loss_grad_acc": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
+                                     c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vn_ppo_env_permutation": (c_int, [c_uint64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vn_ppo_minibatch_gather": (c_int, [P(PpoRollout), P(PpoRollout), c_void_p, c_int, c_int, c_int, c_int,
+                                        c_void_p]),
 })
 
 _lib = None

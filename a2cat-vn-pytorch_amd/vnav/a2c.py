@@ -74,7 +74,7 @@ class A2CTrainer:
                  shaping_anneal_steps=0, gae_lambda=1.0, rp_sampling="sequence", rp_batch=None, rp_skew=0.5,
                  novelty_weight=0.0, first_visit_weight=0.0, novelty_anneal_steps=0, ppo_clip=None, ppo_epochs=4,
                  ppo_value_clip=0.0, ppo_normalize_advantage=True, optimizer="rmsprop", adam_betas=(0.9, 0.999),
-                 adam_epsilon=1e-5):
+                 adam_epsilon=1e-5, ppo_minibatches=1):
         self.env = env
         self.lib = _lib.load()
         # check before every replayed UNREAL pass that the side stream's buffers and gradient
@@ -93,8 +93,9 @@ class A2CTrainer:
         self.seed = int(seed)
         self.group = process_group
         self.world, self.rank = vdist.world_of(process_group)
-        # ppo_clip (None = off): update() runs ppo_epochs full-batch epochs of the clipped surrogate
-        # over the stored rollout instead of one A2C step (_ppo_update, DESIGN.md "PPO epochs").
+        # ppo_clip (None = off): update() runs ppo_epochs epochs of the clipped surrogate over the
+        # stored rollout instead of one A2C step (_ppo_update, DESIGN.md "PPO epochs"): full-batch
+        # epochs, or with ppo_minibatches > 1 shuffled minibatches of whole envs.
         # Each combination refused here is out of scope, not impossible.
         self.ppo = ppo_clip is not None
         self.ppo_epochs = int(ppo_epochs)
@@ -118,6 +119,17 @@ class A2CTrainer:
             if expert_weight is not None:
                 raise ValueError("ppo_clip does not run with expert_weight yet: the expert term lives in the A2C "
                                  "loss-gradient launch")
+        # ppo_minibatches M (1 = off, the full-batch epochs above): every epoch draws one permutation
+        # of the envs on the device and takes M optimiser steps, each on the whole sequences of about
+        # E / M envs (_ppo_minibatch_epochs, DESIGN.md "PPO minibatches")
+        self.ppo_minibatches = int(ppo_minibatches)
+        self._on_ppo_minibatch = None
+        if not 1 <= self.ppo_minibatches <= env.num_envs:
+            raise ValueError("ppo_minibatches must lie in 1..num_envs = %d (a minibatch holds whole envs), got %r"
+                             % (env.num_envs, ppo_minibatches))
+        if self.ppo_minibatches > 1 and not self.ppo:
+            raise ValueError("ppo_minibatches > 1 splits the epochs of a PPO update: it needs ppo_clip (the A2C "
+                             "update takes one step per rollout and has nothing to split)")
         # optimizer: "rmsprop" (the reference's) or "adam" (torch's Adam, vn_adam_step_dev), with
         # plain A2C or PPO, at any world
         if optimizer not in ("rmsprop", "adam"):
@@ -441,11 +453,14 @@ class A2CTrainer:
         # fewer per step
         self._fused_heads = self.recurrent and E <= _FUSED_HEADS_MAX_ENVS
         self._a2c_steps = [self._a2c_step_args(t) for t in range(T)]
+        if self.ppo_minibatches > 1:
+            self._setup_ppo_minibatches()
         env.observe(gather=False)  # refresh the obs row buffers for the first forward
         self.num_updates = 0
         self.total_steps = 0
         self.cuda_graph = bool(cuda_graph)
         self.on_ppo_epoch = None
+        self.on_ppo_minibatch = None
         if self.cuda_graph and self.world > 1:
             if not vdist.capturable(process_group):
                 raise ValueError("cuda_graph=True at world > 1 needs the nccl (RCCL) backend: a gloo all-reduce "
@@ -458,6 +473,62 @@ class A2CTrainer:
         self._graph = None
         self._graph_out = None
         self._graph_gen = None
+
+    def _setup_ppo_minibatches(self):
+        """The split of ppo_minibatches = M > 1: minibatch m of an epoch holds the envs
+        perm[lo_m:lo_{m+1}], lo_m = floor(m E / M). Allocated here: the permutation and the compact
+        [T, ceil(E / M)] copies of the rollout's index and input buffers (a smaller minibatch uses
+        their front). The activations of a minibatch live in the rollout's own buffers at the
+        smaller row count, so nothing of the size of a frame or a feature map is added."""
+        net, E, T, M = self.net, self.env.num_envs, self.num_steps, self.ppo_minibatches
+        A1 = self.A + 1
+        self.mb_bounds = [m * E // M for m in range(M + 1)]
+        sizes = sorted({hi - lo for lo, hi in zip(self.mb_bounds, self.mb_bounds[1:])})
+        cap_e = sizes[-1]
+        cap = T * cap_e
+        i32 = dict(dtype=torch.int32, device=self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.ppo_perm = torch.zeros(E, **i32)
+        self._ppo_seed = vdist.rank_seed(self.seed, self.rank)  # the sampling key; the stream id is the draw's own
+        mb = self.mb = dict(rows_img=torch.zeros(cap, **i32), rows_goal=torch.zeros(cap, **i32),
+                            actions=torch.zeros(cap, **i32), returns=torch.zeros(cap, **f32),
+                            out_old=torch.zeros((cap, OUT_LD), **f32),
+                            dones=torch.zeros(cap, dtype=torch.bool, device=self.device))
+        src = dict(rows_img=self.rows_img, rows_goal=self.rows_goal, actions=self.actions, returns=self.returns,
+                   out_old=self.out_old, dones=self.dones)
+        if self.recurrent:
+            mb.update(masks=torch.zeros(cap, **f32), lra=torch.zeros((cap, A1), **f32))
+            self.mb_hc0 = torch.zeros((2, cap_e, 512), **f32)
+            mb.update(h0=self.mb_hc0[0], c0=self.mb_hc0[1])
+            src.update(masks=self.masks, lra=self.lra, h0=self.h0, c0=self.c0)
+        # goal runs per minibatch where the policy takes them at its row count
+        self._mb_goal_runs = {}
+        if self.dedup_goals:
+            mb["goal_delta"] = torch.zeros(cap, **i32)
+            src["goal_delta"] = self.goal_delta
+            for eb in sizes:
+                if net.goal_runs_supported(T * eb):
+                    g = _lib.GoalRuns()
+                    g.goal_list = self.goal_list.data_ptr()
+                    g.goal_count = self.goal_count[T:T + 1].data_ptr()
+                    g.goal_delta = mb["goal_delta"].data_ptr()
+                    g.run_length = self.goal_run_length.data_ptr()
+                    g.num_envs = eb
+                    self._mb_goal_runs[eb] = g
+        self._mb_src = _lib.PpoRollout(**{k: v.data_ptr() for k, v in src.items()})
+        self._mb_dst = _lib.PpoRollout(**{k: v.data_ptr() for k, v in mb.items()})
+        self._mb_frames = self._frames(mb["rows_img"], mb["rows_goal"])
+        if self.aux_weight > 0:
+            self._mb_aux_targets = AuxTargets(self.aux_table.data_ptr(), mb["rows_img"].data_ptr(),
+                                              mb["rows_goal"].data_ptr())
+        # the scratch of the backward at the minibatch's launch regimes, where it is the larger
+        need = max(net.workspace_floats(T * eb) for eb in sizes)
+        if need > self.workspace.numel():
+            self.workspace = torch.empty(need, **f32)
+        if self.recurrent:
+            need = max(net.lstm_workspace_floats(T, eb) for eb in sizes)
+            if need > self.lstm_ws.numel():
+                self.lstm_ws = torch.empty(need, **f32)
 
     def _setup_unreal(self, unreal, pc_weight, rp_weight, vr_weight, pc_gamma, unreal_envs):
         """Buffers of the UNREAL losses: the first S envs' T + 1 LSTM features (the last row
@@ -1179,6 +1250,19 @@ class A2CTrainer:
                              "replay: use cuda_graph=False")
         self._on_ppo_epoch = fn
 
+    @property
+    def on_ppo_minibatch(self):
+        """None, or a callable(k, m) run after the optimiser step of minibatch m of epoch k (with
+        ppo_minibatches > 1; eager mode only, as on_ppo_epoch)."""
+        return self._on_ppo_minibatch
+
+    @on_ppo_minibatch.setter
+    def on_ppo_minibatch(self, fn):
+        if fn is not None and self.cuda_graph:
+            raise ValueError("on_ppo_minibatch runs host code between the minibatches, which a captured hipGraph "
+                             "cannot replay: use cuda_graph=False")
+        self._on_ppo_minibatch = fn
+
     def _ppo_reforward(self, goals):
         """The stored rollout under the current parameters, into the rollout's own activation
         buffers and self.out: one trunk call over all N rows, recurrent the T LSTM steps from the
@@ -1209,7 +1293,8 @@ class A2CTrainer:
         norm, optimiser step. The carried (h, c) is the behaviour policy's: saved before the first
         re-forward, written into (h0, c0) after the last epoch, so c0 is the rollout's start state
         for every epoch's LSTM backward. No host value enters: the K epochs are captured in the
-        update's one hipGraph."""
+        update's one hipGraph. With ppo_minibatches > 1 the epochs are _ppo_minibatch_epochs'; what
+        is formed once here and the carry are the same."""
         lib, net, P, c_float = self.lib, self.net, _lib.ptr, ctypes.c_float
         E, T, A = self.env.num_envs, self.num_steps, self.A
         N = T * E
@@ -1222,6 +1307,11 @@ class A2CTrainer:
                                             st), "vn_ppo_adv_stats")
         if self.recurrent:
             self._hc_last.copy_(self._hc_all.view(2, T, E, 512)[:, T - 1])
+        if self.ppo_minibatches > 1:
+            self._ppo_minibatch_epochs()
+            if self.recurrent:
+                self._hc0.copy_(self._hc_last)
+            return
         frames = self._frames(self.rows_img, self.rows_goal)
         goals = None
         if self.dedup_goals:  # the rollout's goal runs, for every epoch's re-forward and backward alike
@@ -1252,19 +1342,96 @@ class A2CTrainer:
             else:
                 net.backward_ex(self.params, frames, N, self.acts, N, self.dout, None, dx4, self.grads,
                                 self.workspace, goals=goals)
-            _lib.check(lib.vn_grad_norm(P(self.grads), net.n_params, c_float(1.0), c_float(self.max_gradient_norm),
-                                        P(self.norm_partial), P(self.scalars), st), "vn_grad_norm")
-            if self.optimizer == "adam":
-                self._adam_step(1.0)
-            else:
-                _lib.check(lib.vn_rmsprop_step_dev(P(self.params), P(self.grads), P(self.square_avg), net.n_params,
-                                                   c_float(1.0), P(self.scalars), P(self.lr_dev),
-                                                   c_float(self.rms_alpha), c_float(self.rms_epsilon), st),
-                           "vn_rmsprop_step_dev")
+            self._ppo_optimizer_step()
             if self._on_ppo_epoch is not None:
                 self._on_ppo_epoch(k)
         if self.recurrent:
             self._hc0.copy_(self._hc_last)
+
+    def _ppo_optimizer_step(self):
+        """The norm of the gradient just formed and one clipped optimiser step (world 1)."""
+        lib, n, P, c_float, st = self.lib, self.net.n_params, _lib.ptr, ctypes.c_float, self._stream()
+        _lib.check(lib.vn_grad_norm(P(self.grads), n, c_float(1.0), c_float(self.max_gradient_norm),
+                                    P(self.norm_partial), P(self.scalars), st), "vn_grad_norm")
+        if self.optimizer == "adam":
+            self._adam_step(1.0)
+        else:
+            _lib.check(lib.vn_rmsprop_step_dev(P(self.params), P(self.grads), P(self.square_avg), n, c_float(1.0),
+                                               P(self.scalars), P(self.lr_dev), c_float(self.rms_alpha),
+                                               c_float(self.rms_epsilon), st), "vn_rmsprop_step_dev")
+
+    def _ppo_minibatch_epochs(self):
+        """The epochs of a PPO update in ppo_minibatches = M shuffled minibatches of whole envs
+        (DESIGN.md "PPO minibatches"). Per epoch one permutation of the envs, keyed by the update's
+        counter (sched[2], read on the device); per minibatch one gather of its [T, Eb] sub-rollout
+        into the compact buffers, then the epoch's chain at Eb envs in the rollout's own activation
+        buffers: re-forward from the gathered start states (epoch 0 too: the rollout's stored
+        activations are in the full-batch layout), loss gradient with the mean over the minibatch's
+        own samples and the rollout's advantage statistics, aux heads, LSTM and trunk backward,
+        norm, optimiser step. The sums behind the metrics are cleared when an epoch begins and
+        added to by its minibatches, so they end as the final epoch's over all N samples."""
+        lib, net, P, c_float = self.lib, self.net, _lib.ptr, ctypes.c_float
+        E, T, A, M = self.env.num_envs, self.num_steps, self.A, self.ppo_minibatches
+        N = T * E
+        st = self._stream()
+        mb, frames = self.mb, self._mb_frames
+        counter = self.sched[2:3]
+        x5 = net.x5(self.acts, N) if self.recurrent else None
+        for k in range(self.ppo_epochs):
+            _lib.check(lib.vn_ppo_env_permutation(self._ppo_seed, P(counter), k, E, 32, P(self.ppo_perm), st),
+                       "vn_ppo_env_permutation")
+            self.stats.zero_()
+            self.ppo_stats.zero_()
+            if self.aux_weight > 0:
+                self.aux_stats.zero_()
+            for m in range(M):
+                lo, eb = self.mb_bounds[m], self.mb_bounds[m + 1] - self.mb_bounds[m]
+                nb = T * eb
+                _lib.check(lib.vn_ppo_minibatch_gather(ctypes.byref(self._mb_src), ctypes.byref(self._mb_dst),
+                                                       P(self.ppo_perm[lo:]), eb, T, E, A, st),
+                           "vn_ppo_minibatch_gather")
+                goals = self._mb_goal_runs.get(eb)
+                if goals is not None:  # this minibatch's goal runs, from its gathered dones
+                    _lib.check(lib.vn_goal_runs_rollout(P(mb["dones"]), T, eb, P(self.goal_list),
+                                                        P(self.goal_run_length), P(self.goal_count[T:T + 1]), st),
+                               "vn_goal_runs_rollout")
+                if self.recurrent:
+                    net.forward(self.params, frames, nb, self.acts, N, 0, None, goals=goals)
+                    for t in range(T):
+                        sl = slice(t * eb, (t + 1) * eb)
+                        hp = mb["h0"] if t == 0 else self.h_all[(t - 1) * eb:t * eb]
+                        cp = mb["c0"] if t == 0 else self.c_all[(t - 1) * eb:t * eb]
+                        net.lstm_step(self.params, eb, x5[sl], mb["lra"][sl], mb["masks"][sl], hp, cp, self.xcat[sl],
+                                      self.gates, self.lstm_acts[sl], self.c_all[sl], self.h_all[sl])
+                    net.heads(self.params, self.h_all, nb, self.out)
+                else:
+                    net.forward(self.params, frames, nb, self.acts, N, 0, self.out, goals=goals)
+                _lib.check(lib.vn_ppo_loss_grad_acc(
+                    P(self.out), P(mb["out_old"]), P(mb["actions"]), P(mb["returns"]),
+                    P(self.adv_stats) if self.ppo_normalize_advantage else None, nb, A, c_float(self.ppo_clip),
+                    c_float(self.ppo_value_clip), c_float(self.value_coefficient), c_float(self.entropy_coefficient),
+                    P(self.dout), P(self.stats), P(self.ppo_stats), st), "vn_ppo_loss_grad_acc")
+                dx4 = None
+                if self.aux_weight > 0:  # the deconv heads on the minibatch: targets by its gathered rows
+                    net.aux_forward_loss_grad(self.params, self.acts, N, nb, self.a1, self.pred, self._mb_aux_targets,
+                                              self.aux_weight, self.dpred, self.aux_stats, self.aux_ws)
+                    net.aux_backward(self.params, self.acts, N, nb, self.a1, self.dpred, self.grads, self.dx4,
+                                     self.aux_ws)
+                    dx4 = self.dx4
+                if self.recurrent:
+                    net.lstm_backward(self.params, T, eb, self.dout, self.h_all, self.xcat, self.lstm_acts, self.c_all,
+                                      mb["c0"], mb["masks"], x5, self.dz5, self.grads, self.lstm_ws, dh_extra=None,
+                                      extra_envs=0)
+                    net.backward_ex(self.params, frames, nb, self.acts, N, None, self.dz5, dx4, self.grads,
+                                    self.workspace, goals=goals)
+                else:
+                    net.backward_ex(self.params, frames, nb, self.acts, N, self.dout, None, dx4, self.grads,
+                                    self.workspace, goals=goals)
+                self._ppo_optimizer_step()
+                if self._on_ppo_minibatch is not None:
+                    self._on_ppo_minibatch(k, m)
+            if self._on_ppo_epoch is not None:
+                self._on_ppo_epoch(k)
 
     def _buckets_split(self):
         """Two gradient buckets when the head bucket is final before the trunk backward:

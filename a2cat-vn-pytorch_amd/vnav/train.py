@@ -145,10 +145,11 @@ class Experiment:
     novelty_anneal_steps = 0
     visit_counts = False
     # PPO epochs over the stored rollout (A2CTrainer ppo_clip / ppo_epochs / ppo_value_clip /
-    # ppo_normalize_advantage): clip None = off, the one A2C step per rollout; and the optimiser
-    # (A2CTrainer optimizer): "rmsprop" or "adam"
+    # ppo_normalize_advantage / ppo_minibatches): clip None = off, the one A2C step per rollout;
+    # minibatches 1 = full-batch epochs; and the optimiser (A2CTrainer optimizer): "rmsprop" or "adam"
     ppo_clip = None
     ppo_epochs = 4
+    ppo_minibatches = 1
     ppo_value_clip = 0.0
     ppo_normalize_advantage = True
     optimizer = "rmsprop"
@@ -198,7 +199,8 @@ class Experiment:
                           novelty_weight=self.novelty_weight, first_visit_weight=self.first_visit_weight,
                           novelty_anneal_steps=self.novelty_anneal_steps, ppo_clip=self.ppo_clip,
                           ppo_epochs=self.ppo_epochs, ppo_value_clip=self.ppo_value_clip,
-                          ppo_normalize_advantage=self.ppo_normalize_advantage, optimizer=self.optimizer)
+                          ppo_normalize_advantage=self.ppo_normalize_advantage, optimizer=self.optimizer,
+                          ppo_minibatches=self.ppo_minibatches)
 
     def _setup(self):
         if self.trainer is None:
@@ -593,6 +595,9 @@ def main(argv=None):
                    help="PPO: --ppo-epochs full-batch epochs of the surrogate clipped at 1 +- C over every rollout "
                         "(default: one A2C step per rollout)")
     p.add_argument("--ppo-epochs", type=int, default=None, metavar="K", help="--ppo-clip: epochs per rollout (default 4)")
+    p.add_argument("--ppo-minibatches", type=int, default=None, metavar="M",
+                   help="--ppo-clip: split every epoch into M shuffled minibatches of whole envs, one optimiser step "
+                        "each (default 1: full-batch epochs; at most the number of envs)")
     p.add_argument("--ppo-value-clip", type=float, default=None, metavar="CV",
                    help="--ppo-clip: clip the critic's move from its rollout value at CV (default 0: off)")
     p.add_argument("--no-adv-norm", action="store_true",
@@ -600,12 +605,15 @@ def main(argv=None):
     p.add_argument("--optimizer", default=None, choices=("adam", "rmsprop"),
                    help="the optimiser of the update (default rmsprop, the reference's)")
     a = p.parse_args(argv)
-    if a.ppo_clip is None and (a.ppo_epochs is not None or a.ppo_value_clip is not None or a.no_adv_norm):
-        p.error("--ppo-epochs / --ppo-value-clip / --no-adv-norm need --ppo-clip")
+    if a.ppo_clip is None and (a.ppo_epochs is not None or a.ppo_value_clip is not None or a.no_adv_norm or
+                               a.ppo_minibatches is not None):
+        p.error("--ppo-epochs / --ppo-minibatches / --ppo-value-clip / --no-adv-norm need --ppo-clip")
     if a.ppo_clip is not None and not a.ppo_clip > 0:
         p.error("--ppo-clip must be > 0")
     if a.ppo_epochs is not None and a.ppo_epochs < 1:
         p.error("--ppo-epochs must be at least 1")
+    if a.ppo_minibatches is not None and a.ppo_minibatches < 1:
+        p.error("--ppo-minibatches must be at least 1")
     if a.ppo_value_clip is not None and a.ppo_value_clip < 0:
         p.error("--ppo-value-clip must be >= 0")
     for flag, v in (("--novelty-weight", a.novelty_weight), ("--first-visit-weight", a.first_visit_weight),
@@ -675,7 +683,7 @@ def main(argv=None):
     if a.visit_counts:
         over["visit_counts"] = True
     for key, v in (("ppo_clip", a.ppo_clip), ("ppo_epochs", a.ppo_epochs), ("ppo_value_clip", a.ppo_value_clip),
-                   ("optimizer", a.optimizer)):
+                   ("ppo_minibatches", a.ppo_minibatches), ("optimizer", a.optimizer)):
         if v is not None:
             over[key] = v
     if a.no_adv_norm:

@@ -1033,6 +1033,55 @@ int vn_ppo_loss_grad(const float* out, const float* out_old, const int32_t* acti
                      const float* adv_stats2_dev, int n, int num_actions, float clip, float value_clip,
                      float value_coef, float entropy_coef, float* dout, float* stats4, float* ppo_stats4,
                      vn_stream_t stream);
+/* vn_ppo_loss_grad without the clearing: stats4 and ppo_stats4 are added to, so the launches of one
+ * epoch's minibatches leave the epoch's sums (the caller clears them before the first). dout and
+ * the 1 / n of the means are this call's n samples' own. Same arguments, same refusals. */
+int vn_ppo_loss_grad_acc(const float* out, const float* out_old, const int32_t* actions, const float* returns,
+                         const float* adv_stats2_dev, int n, int num_actions, float clip, float value_clip,
+                         float value_coef, float entropy_coef, float* dout, float* stats4, float* ppo_stats4,
+                         vn_stream_t stream);
+
+/* PPO minibatches (DESIGN.md "PPO minibatches", csrc/vn_ppo_minibatch.hip): an epoch's shuffled
+ * split of the envs and the compaction of one minibatch's sub-rollout, both on the device.
+ *
+ * vn_ppo_env_permutation: perm [num_envs] int32 = the stable argsort of the envs' keys, ties by
+ * env index (numpy's argsort(keys, kind="stable") exactly). Key of env e in epoch k: the first
+ * output word of Philox4x32-10 on the counter (k num_envs + e, ctr_lo, ctr_hi, 7 = STREAM_PPO)
+ * under the key (seed_lo, seed_hi), masked to its low key_bits bits (32 = the whole word; fewer
+ * force ties); ctr = *counter_dev, an int64 read on the device (the update's counter base of
+ * vn_a2c_rollout_begin's schedule). One launch of ceil(num_envs / 256) workgroups, rank by
+ * counting over keys staged in LDS VN_PPO_PERM_TILE at a time: no atomics, every slot written
+ * once, the same bits on every run. VN_EINVAL, nothing written: a NULL pointer, epoch < 0,
+ * num_envs < 1, key_bits outside 1..32, (epoch + 1) num_envs >= 2^32. */
+#define VN_PPO_PERM_TILE 1024
+int vn_ppo_env_permutation(uint64_t seed, const int64_t* counter_dev, int epoch, int num_envs, int key_bits,
+                           int32_t* perm, vn_stream_t stream);
+/* The buffers of a rollout in time-major layout, row t E + e: the [T, E] source, or the compact
+ * [T, count] destination (row t count + j). */
+typedef struct vn_ppo_rollout {
+  int32_t* rows_img;    /* [T E] frame rows (vn_frames.image_rows) */
+  int32_t* rows_goal;   /* [T E] */
+  int32_t* actions;     /* [T E] */
+  float* returns;       /* [T E] */
+  float* out_old;       /* [T E][8] the behaviour policy's head outputs, 16-byte aligned */
+  uint8_t* dones;       /* [T E] */
+  float* masks;         /* [T E] LSTM episode masks (NULL with lra, h0, c0: a feed-forward policy) */
+  float* lra;           /* [T E][A + 1] last action one-hot | last reward */
+  float* h0;            /* [E][512] the state entering the rollout, 16-byte aligned */
+  float* c0;            /* [E][512] */
+  int32_t* goal_delta;  /* [T E] vn_goal_runs.goal_delta (may be NULL): scaled by count / E on the way */
+} vn_ppo_rollout;
+/* dst row t count + j = src row t num_envs + envs[j] for every buffer above (h0 / c0: row j =
+ * row envs[j]), envs [count] int32 on the device (a slice of vn_ppo_env_permutation's perm).
+ * goal_delta, a multiple of the sample stride, is rescaled to the destination's stride. One
+ * launch; every destination element is written once by a plain vector store, rows past T count
+ * are not touched; an envs[j] outside [0, num_envs) writes nothing for that env. VN_EINVAL,
+ * nothing written: a NULL struct or envs, a NULL rows / actions / returns / out_old / dones on
+ * either side, some but not all of dst's masks / lra / h0 / c0, a dst buffer whose src is NULL,
+ * count outside 1..num_envs, T < 1, num_actions outside 1..7, a misaligned out_old / h0 / c0. */
+int vn_ppo_minibatch_gather(const vn_ppo_rollout* src, const vn_ppo_rollout* dst, const int32_t* envs, int count,
+                            int T, int num_envs, int num_actions, vn_stream_t stream);
+
 /* torch's Adam without weight decay or amsgrad on the flat buffers, vn_rmsprop_step_dev's shape:
  *   g = grads (scalars2[1] scale); m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g^2;
  *   t = *step_dev + 1; bc1 = 1 - beta1^t and bc2 = 1 - beta2^t formed in fp64 on the device;

@@ -18,9 +18,17 @@ updates, feed-forward 84x84, limit 30, the seeds of shaping_bench / visit_bench)
 the finished episodes over the last 20 updates and their number, A2C against PPO K = 4 (RMSprop at
 the same learning rate, and Adam), 3 seeds each.
 
+--minibatches M [M ...] (DESIGN.md "PPO minibatches"): the same two modes on the minibatch split.
+cost: PPO with 1 and 4 epochs at every M given (4096 envs; the 4-env batch at M = 1 and 2), variants
+alternating as above; from the medians the cost of one minibatch step, (K4 - K1) / (3 M), beside
+1 / M of a full-batch epoch, and the back-to-back launch intervals of vn_ppo_env_permutation and
+vn_ppo_minibatch_gather on their own. learn: PPO K = 4 with Adam at every M given. Writes
+<out>/ppo_minibatch_bench.json or <out>/ppo_minibatch_learn.json (default <out>:
+profiles/ppo_minibatch).
+
 Writes <out>/ppo_bench.json or <out>/ppo_learn.json and prints the same JSON line.
 
-    python tools/ppo_bench.py [--mode cost|learn] [--rounds 5] [--out DIR]
+    python tools/ppo_bench.py [--mode cost|learn] [--minibatches M [M ...]] [--rounds 5] [--out DIR]
 """
 import argparse
 import json
@@ -66,7 +74,97 @@ def time_update(kw, scenes, E, graph, warmup, K, dev):
     return ms
 
 
+def launch_intervals(dev, calls=200):
+    """Microseconds per call of the two minibatch launches on their own, back to back on one
+    stream between one event pair (an interval, not a kernel time: it cannot go below the
+    launch rate)."""
+    import ctypes
+
+    from vnav import _lib
+    from vnav.policy import OUT_LD
+    lib, P, st = _lib.load(), _lib.ptr, _lib.stream_ptr(dev)
+    T, E, A = 20, 4096, 4
+    i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+    ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+    perm = torch.zeros(E, **i32)
+
+    def timed(fn):
+        for _ in range(10):
+            fn()
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(dev)
+        ev0.record()
+        for _ in range(calls):
+            fn()
+        ev1.record()
+        torch.cuda.synchronize(dev)
+        return ev0.elapsed_time(ev1) * 1000.0 / calls
+
+    out = {"unit": "us per call, %d calls back to back" % calls, "T": T, "E": E}
+    for n in (4096, 32768):
+        big = torch.zeros(n, **i32)
+        out["env_permutation_E%d" % n] = timed(lambda: _lib.check(
+            lib.vn_ppo_env_permutation(1, P(ctr), 0, n, 32, P(big), st), "vn_ppo_env_permutation"))
+    _lib.check(lib.vn_ppo_env_permutation(1, P(ctr), 0, E, 32, P(perm), st), "vn_ppo_env_permutation")
+
+    def bufs(envs):
+        n = T * envs
+        return dict(rows_img=torch.zeros(n, **i32), rows_goal=torch.zeros(n, **i32), actions=torch.zeros(n, **i32),
+                    returns=torch.zeros(n, **f32), out_old=torch.zeros((n, OUT_LD), **f32),
+                    dones=torch.zeros(n, dtype=torch.bool, device=dev), masks=torch.zeros(n, **f32),
+                    lra=torch.zeros((n, A + 1), **f32), h0=torch.zeros((envs, 512), **f32),
+                    c0=torch.zeros((envs, 512), **f32))
+
+    src = bufs(E)
+    s = _lib.PpoRollout(**{k: v.data_ptr() for k, v in src.items()})
+    for M in (4, 16):
+        eb = E // M
+        dst = bufs(eb)
+        d = _lib.PpoRollout(**{k: v.data_ptr() for k, v in dst.items()})
+        out["minibatch_gather_M%d" % M] = timed(lambda: _lib.check(
+            lib.vn_ppo_minibatch_gather(ctypes.byref(s), ctypes.byref(d), P(perm), eb, T, E, A, st),
+            "vn_ppo_minibatch_gather"))
+    return out
+
+
+def cost_minibatches(a, dev):
+    import vnav
+    K = 4
+    res = {"tool": "ppo_bench", "mode": "cost", "minibatches": a.minibatches,
+           "config": {"seed": SEED, "rounds": a.rounds, "updates": a.updates, "update_warmup": a.update_warmup,
+                      "epochs": [1, K]},
+           "update": {"unit": "ms per A2CTrainer.step() (device, one event pair)"}}
+    points = (("envs4096_84_lstm", [vnav.synthetic_scene(k) for k in range(20)], 4096, False, 1,
+               sorted(set(a.minibatches) | {1})),
+              ("envs4_174_graph", [vnav.synthetic_scene(0, frame_shape=(174, 174, 3))], 4, True, 10, [1, 2]))
+    for name, sc, E, graph, mult, Ms in points:
+        variants = {"k%d_m%d" % (k, M): dict(ppo_clip=0.2, ppo_epochs=k, ppo_minibatches=M) for M in Ms for k in (1, K)}
+        ms = {v: [] for v in variants}
+        for _ in range(a.rounds):
+            for v, kw in variants.items():
+                ms[v].append(time_update(kw, sc, E, graph, a.update_warmup, a.updates * mult, dev))
+        sp = {v: spread(ms[v]) for v in variants}
+        med = {v: sp[v]["median"] for v in variants}
+        full_epoch = (med["k%d_m1" % K] - med["k1_m1"]) / (K - 1)  # one re-forwarding full-batch epoch
+        derived = {}
+        for M in Ms:
+            if M == 1:
+                continue
+            step = (med["k%d_m%d" % (K, M)] - med["k1_m%d" % M]) / ((K - 1) * M)
+            derived["m%d" % M] = {
+                "k4_minus_full_batch_k4_ms": med["k%d_m%d" % (K, M)] - med["k%d_m1" % K],
+                "minibatch_step_ms": step, "full_batch_epoch_over_m_ms": full_epoch / M,
+                "regime_gap_ms": step - full_epoch / M, "epoch_ms": step * M,
+                "epoch_over_full_batch_epoch": step * M / full_epoch}
+        res["update"][name] = dict(sp, envs=E, frame=list(sc[0].frame_shape), cuda_graph=graph,
+                                   updates_timed=a.updates * mult, full_batch_epoch_ms=full_epoch, derived=derived)
+    res["launches"] = launch_intervals(dev)
+    return res, "ppo_minibatch_bench.json"
+
+
 def cost(a, dev):
+    if a.minibatches:
+        return cost_minibatches(a, dev)
     import vnav
     res = {"tool": "ppo_bench", "mode": "cost",
            "config": {"seed": SEED, "rounds": a.rounds, "updates": a.updates, "update_warmup": a.update_warmup,
@@ -118,17 +216,22 @@ def learn_run(kw, seed, updates, dev):
 
 
 def learn(a, dev):
+    variants, name = LEARN, "ppo_learn.json"
+    if a.minibatches:
+        variants = {"ppo4_adam_m%d" % M: dict(ppo_clip=0.2, ppo_epochs=4, optimizer="adam", ppo_minibatches=M)
+                    for M in a.minibatches}
+        name = "ppo_minibatch_learn.json"
     res = {"tool": "ppo_bench", "mode": "learn",
            "config": {"task": "synthetic_scene(0, grid=6), goal 7, limit 30", "envs": 16, "num_steps": 20,
-                      "updates": a.learn_updates, "seeds": [0, 1, 2], "variants": LEARN,
+                      "updates": a.learn_updates, "seeds": [0, 1, 2], "variants": variants,
                       "measure": "successes / finished episodes over the last 20 updates, and their number; "
                                  "approx_kl and clip_fraction of the last update"},
            "runs": {}}
-    for name, kw in LEARN.items():
+    for v, kw in variants.items():
         rows = [learn_run(kw, seed, a.learn_updates, dev) for seed in (0, 1, 2)]
-        res["runs"][name] = {"success_rate": [r[0] for r in rows], "episodes": [r[1] for r in rows],
+        res["runs"][v] = {"success_rate": [r[0] for r in rows], "episodes": [r[1] for r in rows],
                              "approx_kl": [r[2] for r in rows], "clip_fraction": [r[3] for r in rows]}
-    return res, "ppo_learn.json"
+    return res, name
 
 
 def main():
@@ -138,8 +241,14 @@ def main():
     ap.add_argument("--updates", type=int, default=30)
     ap.add_argument("--update-warmup", type=int, default=5)
     ap.add_argument("--learn-updates", type=int, default=120)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ppo"))
+    ap.add_argument("--minibatches", type=int, nargs="+", default=None, metavar="M",
+                    help="measure the minibatch split at these M (writes ppo_minibatch_*.json)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.minibatches and min(a.minibatches) < 1:
+        ap.error("--minibatches must be at least 1")
+    if a.out is None:
+        a.out = os.path.join(REPO, "profiles", "ppo_minibatch" if a.minibatches else "ppo")
     if not torch.cuda.is_available():
         raise SystemExit("ppo_bench needs the GPU (no CPU timing)")
     dev = torch.device("cuda", 0)
