@@ -333,6 +333,11 @@ SIGNATURES.update({
     "vn_ppo_env_permutation": (c_int, [c_uint64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vn_ppo_minibatch_gather": (c_int, [P(PpoRollout), P(PpoRollout), c_void_p, c_int, c_int, c_int, c_int,
                                         c_void_p]),
+    "vn_ppo_kl_gate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "vn_adam_step_gated": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p,
+                                   c_void_p, c_float, c_float, c_float, c_void_p, c_void_p]),
+    "vn_rmsprop_step_gated": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_float,
+                                      c_float, c_void_p, c_void_p]),
 })
 
 _lib = None

@@ -74,7 +74,7 @@ class A2CTrainer:
                  shaping_anneal_steps=0, gae_lambda=1.0, rp_sampling="sequence", rp_batch=None, rp_skew=0.5,
                  novelty_weight=0.0, first_visit_weight=0.0, novelty_anneal_steps=0, ppo_clip=None, ppo_epochs=4,
                  ppo_value_clip=0.0, ppo_normalize_advantage=True, optimizer="rmsprop", adam_betas=(0.9, 0.999),
-                 adam_epsilon=1e-5, ppo_minibatches=1):
+                 adam_epsilon=1e-5, ppo_target_kl=None, ppo_kl_host_stop=False, ppo_minibatches=1):
         self.env = env
         self.lib = _lib.load()
         # check before every replayed UNREAL pass that the side stream's buffers and gradient
@@ -130,6 +130,28 @@ class A2CTrainer:
         if self.ppo_minibatches > 1 and not self.ppo:
             raise ValueError("ppo_minibatches > 1 splits the epochs of a PPO update: it needs ppo_clip (the A2C "
                              "update takes one step per rollout and has nothing to split)")
+        # ppo_target_kl (None = off): before every optimiser step of a PPO update the k3 estimate of
+        # KL(old || new) over the step's own samples is formed on the device (vn_ppo_kl_gate), and
+        # once it exceeds 1.5 * target (the rule of Stable-Baselines3 and Spinning Up) that step and
+        # every later one of the update change nothing (DESIGN.md "PPO target KL"). The launches
+        # still run, so the update stays one captured graph; ppo_kl_host_stop (eager only) reads the
+        # flag after each check and leaves the loops instead, to the same bits.
+        self.ppo_target_kl = None if ppo_target_kl is None else float(ppo_target_kl)
+        self.ppo_kl_host_stop = bool(ppo_kl_host_stop)
+        if self.ppo_target_kl is not None:
+            if not self.ppo:
+                raise ValueError("ppo_target_kl stops the epochs of a PPO update early: it needs ppo_clip (the A2C "
+                                 "update takes one step per rollout and has nothing to stop)")
+            if not self.ppo_target_kl > 0.0:  # NaN too
+                raise ValueError("ppo_target_kl must be > 0, got %r" % (ppo_target_kl,))
+            with np.errstate(over="ignore"):  # a target past fp32's range is a limit of inf: never stopped
+                self._kl_limit = float(np.float32(1.5 * self.ppo_target_kl))
+        if self.ppo_kl_host_stop:
+            if self.ppo_target_kl is None:
+                raise ValueError("ppo_kl_host_stop reads the stop flag of ppo_target_kl: it needs ppo_target_kl")
+            if cuda_graph:
+                raise ValueError("ppo_kl_host_stop runs host code between the epochs, which a captured hipGraph "
+                                 "cannot replay: use cuda_graph=False")
         # optimizer: "rmsprop" (the reference's) or "adam" (torch's Adam, vn_adam_step_dev), with
         # plain A2C or PPO, at any world
         if optimizer not in ("rmsprop", "adam"):
@@ -187,6 +209,11 @@ class A2CTrainer:
             self.out_old = torch.zeros((N, OUT_LD), dtype=torch.float32, **kw)
             self.adv_stats = torch.zeros(2, dtype=torch.float32, **kw)
             self.ppo_stats = torch.zeros(4, dtype=torch.float32, **kw)
+            if self.ppo_target_kl is not None:
+                # vn_ppo_kl_gate's [stopped, steps allowed] and [the last check's KL, the KL that
+                # stopped the update], zeroed when an update begins
+                self.kl_gate = torch.zeros(2, dtype=torch.int32, **kw)
+                self.kl_dev = torch.zeros(2, dtype=torch.float32, **kw)
         self.norm_partial = torch.zeros(512, dtype=torch.float64, **kw)
         self.scalars = torch.zeros(2, dtype=torch.float32, **kw)
         self.episode_stats = torch.zeros(3, dtype=torch.float32, **kw)  # count, return sum, length sum
@@ -312,7 +339,8 @@ class A2CTrainer:
             self.visit_seen = torch.zeros(2, dtype=torch.int64, **kw)  # [states seen, visits] of this rank
         self._metric_layout = metric_layout(bool(unreal), self.nav_metrics, self.expert, self.geo_curriculum is not None,
                                             self.shaping, self.rp_skewed, self.novelty,
-                                            ppo=self.ppo)  # step()'s vector: {segment: (offset, width)}
+                                            ppo=self.ppo,  # step()'s vector: {segment: (offset, width)}
+                                            ppo_kl=self.ppo_target_kl is not None)
         self.workspace = torch.empty(self.net.workspace_floats(N), dtype=torch.float32, **kw)
         if self.recurrent:
             X = self.net.lstm["xcat"]
@@ -1294,7 +1322,9 @@ class A2CTrainer:
         re-forward, written into (h0, c0) after the last epoch, so c0 is the rollout's start state
         for every epoch's LSTM backward. No host value enters: the K epochs are captured in the
         update's one hipGraph. With ppo_minibatches > 1 the epochs are _ppo_minibatch_epochs'; what
-        is formed once here and the carry are the same."""
+        is formed once here and the carry are the same. With ppo_target_kl every optimiser step has
+        the KL check in front of it (_ppo_kl_gate, DESIGN.md "PPO target KL"): its buffers are zeroed
+        here, and once it has fired the remaining epochs run their launches and change nothing."""
         lib, net, P, c_float = self.lib, self.net, _lib.ptr, ctypes.c_float
         E, T, A = self.env.num_envs, self.num_steps, self.A
         N = T * E
@@ -1307,6 +1337,9 @@ class A2CTrainer:
                                             st), "vn_ppo_adv_stats")
         if self.recurrent:
             self._hc_last.copy_(self._hc_all.view(2, T, E, 512)[:, T - 1])
+        if self.ppo_target_kl is not None:  # the stop is this update's own
+            self.kl_gate.zero_()
+            self.kl_dev.zero_()
         if self.ppo_minibatches > 1:
             self._ppo_minibatch_epochs()
             if self.recurrent:
@@ -1321,6 +1354,8 @@ class A2CTrainer:
         for k in range(self.ppo_epochs):
             if k > 0:
                 self._ppo_reforward(goals)
+            if self._ppo_kl_gate(self.out, self.out_old, self.actions, N):
+                break
             _lib.check(lib.vn_ppo_loss_grad(
                 P(self.out), P(self.out_old), P(self.actions), P(self.returns),
                 P(self.adv_stats) if self.ppo_normalize_advantage else None, N, A, c_float(self.ppo_clip),
@@ -1348,11 +1383,38 @@ class A2CTrainer:
         if self.recurrent:
             self._hc0.copy_(self._hc_last)
 
+    def _ppo_kl_gate(self, out, out_old, actions, n):
+        """The target-KL check in front of one optimiser step: vn_ppo_kl_gate over the step's own n
+        samples, between the forward that produced ``out`` and the loss-gradient launch. Once it
+        has fired, the gated optimiser steps of the update change nothing. Returns True only with
+        ppo_kl_host_stop, when the host has read the flag and found it set: the caller then leaves
+        its loops, which ends with the same bits as running them out."""
+        if self.ppo_target_kl is None:
+            return False
+        P = _lib.ptr
+        _lib.check(self.lib.vn_ppo_kl_gate(P(out), P(out_old), P(actions), n, self.A, ctypes.c_float(self._kl_limit),
+                                           P(self.kl_gate), P(self.kl_dev), self._stream()), "vn_ppo_kl_gate")
+        return self.ppo_kl_host_stop and bool(self.kl_gate[0].item())  # a 4-byte copy and a sync
+
     def _ppo_optimizer_step(self):
-        """The norm of the gradient just formed and one clipped optimiser step (world 1)."""
+        """The norm of the gradient just formed and one clipped optimiser step (world 1); with
+        ppo_target_kl the step that reads the stop flag on the device."""
         lib, n, P, c_float, st = self.lib, self.net.n_params, _lib.ptr, ctypes.c_float, self._stream()
         _lib.check(lib.vn_grad_norm(P(self.grads), n, c_float(1.0), c_float(self.max_gradient_norm),
                                     P(self.norm_partial), P(self.scalars), st), "vn_grad_norm")
+        if self.ppo_target_kl is not None:
+            if self.optimizer == "adam":
+                _lib.check(lib.vn_adam_step_gated(P(self.params), P(self.grads), P(self.exp_avg), P(self.exp_avg_sq), n,
+                                                  c_float(1.0), P(self.scalars), P(self.lr_dev), P(self.adam_step),
+                                                  c_float(self.adam_betas[0]), c_float(self.adam_betas[1]),
+                                                  c_float(self.adam_epsilon), P(self.kl_gate), st),
+                           "vn_adam_step_gated")
+            else:
+                _lib.check(lib.vn_rmsprop_step_gated(P(self.params), P(self.grads), P(self.square_avg), n, c_float(1.0),
+                                                     P(self.scalars), P(self.lr_dev), c_float(self.rms_alpha),
+                                                     c_float(self.rms_epsilon), P(self.kl_gate), st),
+                           "vn_rmsprop_step_gated")
+            return
         if self.optimizer == "adam":
             self._adam_step(1.0)
         else:
@@ -1377,6 +1439,7 @@ class A2CTrainer:
         mb, frames = self.mb, self._mb_frames
         counter = self.sched[2:3]
         x5 = net.x5(self.acts, N) if self.recurrent else None
+        stopped = False  # ppo_kl_host_stop: the host has seen the stop flag set
         for k in range(self.ppo_epochs):
             _lib.check(lib.vn_ppo_env_permutation(self._ppo_seed, P(counter), k, E, 32, P(self.ppo_perm), st),
                        "vn_ppo_env_permutation")
@@ -1406,6 +1469,10 @@ class A2CTrainer:
                     net.heads(self.params, self.h_all, nb, self.out)
                 else:
                     net.forward(self.params, frames, nb, self.acts, N, 0, self.out, goals=goals)
+                # the KL over the minibatch's own samples against its gathered out_old
+                stopped = self._ppo_kl_gate(self.out, mb["out_old"], mb["actions"], nb)
+                if stopped:
+                    break
                 _lib.check(lib.vn_ppo_loss_grad_acc(
                     P(self.out), P(mb["out_old"]), P(mb["actions"]), P(mb["returns"]),
                     P(self.adv_stats) if self.ppo_normalize_advantage else None, nb, A, c_float(self.ppo_clip),
@@ -1430,6 +1497,8 @@ class A2CTrainer:
                 self._ppo_optimizer_step()
                 if self._on_ppo_minibatch is not None:
                     self._on_ppo_minibatch(k, m)
+            if stopped:  # left inside epoch k: it did not finish, its hook does not run
+                break
             if self._on_ppo_epoch is not None:
                 self._on_ppo_epoch(k)
 
@@ -1541,6 +1610,9 @@ class A2CTrainer:
         }
         if self.ppo:  # the final epoch's sums (fp32 sums of at most N terms; the vector's width)
             tails["ppo"] = lambda: [self.ppo_stats.to(f64 if self.shaping else torch.float32)]
+        if self.ppo_target_kl is not None:  # steps allowed, stopped, the KL at the stop (0 when not stopped)
+            wide = f64 if self.shaping else torch.float32
+            tails["ppo_kl"] = lambda: [self.kl_gate.flip(0).to(wide), self.kl_dev[1:].to(wide)]
         for name in list(layout)[1:]:
             parts = tails[name]()
             m = torch.cat([m.to(parts[0].dtype)] + parts)
@@ -1612,6 +1684,12 @@ class A2CTrainer:
         if self.ppo:  # the final epoch's means over the N samples
             ppo = dict(zip(("approx_kl", "clip_fraction", "ratio_mean", "value_clip_fraction"),
                            (x / N for x in seg["ppo"])))
+        if self.ppo_target_kl is not None:
+            # the optimiser steps the update took before the KL check fired (ppo_epochs *
+            # ppo_minibatches when it did not). With ppo_kl_host_stop the loops end at the stop, so
+            # approx_kl and the other sums above are those of the last epoch that ran (with
+            # minibatches: of its minibatches that ran) instead of the final one's.
+            ppo.update(zip(("ppo_steps", "kl_stopped", "kl_at_stop"), seg["ppo_kl"]))
         dt = time.perf_counter() - t0
         return {
             "step": self.total_steps, "updates": self.num_updates,

@@ -3,7 +3,7 @@ once: _update_metrics assembles the vector from it, step() decodes it by segment
 
 
 def metric_layout(unreal=False, nav_metrics=False, expert=False, geo_curriculum=False, shaping=False,
-                  rp_sampling=False, novelty=False, ppo=False):
+                  rp_sampling=False, novelty=False, ppo=False, ppo_kl=False):
     """{segment: (offset, width)} of the vector under these trainer flags, in the vector's order
     (its width: the last segment's offset + width). fp64 with ``shaping``, whose distance sums
     are exact there, fp32 otherwise."""
@@ -24,6 +24,11 @@ def metric_layout(unreal=False, nav_metrics=False, expert=False, geo_curriculum=
         # the final PPO epoch (vn_ppo_loss_grad's ppo_stats4), sums over the N samples: the k3
         # estimate of KL(old || new), samples with |r - 1| > clip, the ratio, value-clipped samples
         ("ppo", 4, ppo),
+        # the target-KL stop (vn_ppo_kl_gate's gate_dev and kl_dev): ppo_steps = the optimiser steps
+        # the update was allowed, kl_stopped = 1 when a check fired, kl_at_stop = the KL that fired it
+        # (0 when none did). With ppo_kl_host_stop the epochs end at the stop, so the "ppo" sums are
+        # then those of the last epoch that ran, not of the final one.
+        ("ppo_kl", 3, ppo_kl),
     )
     layout, offset = {}, 0
     for name, width, on in segments:

@@ -153,6 +153,9 @@ class Experiment:
     ppo_value_clip = 0.0
     ppo_normalize_advantage = True
     optimizer = "rmsprop"
+    # the target-KL early stop of a PPO update (A2CTrainer ppo_target_kl / ppo_kl_host_stop): None = off
+    ppo_target_kl = None
+    ppo_kl_host_stop = False
 
     def __init__(self, env_kwargs=None, model_kwargs=None, save_dir=None, seed=0, device=None, logger=print,
                  **overrides):
@@ -200,7 +203,8 @@ class Experiment:
                           novelty_anneal_steps=self.novelty_anneal_steps, ppo_clip=self.ppo_clip,
                           ppo_epochs=self.ppo_epochs, ppo_value_clip=self.ppo_value_clip,
                           ppo_normalize_advantage=self.ppo_normalize_advantage, optimizer=self.optimizer,
-                          ppo_minibatches=self.ppo_minibatches)
+                          ppo_minibatches=self.ppo_minibatches, ppo_target_kl=self.ppo_target_kl,
+                          ppo_kl_host_stop=self.ppo_kl_host_stop)
 
     def _setup(self):
         if self.trainer is None:
@@ -604,7 +608,21 @@ def main(argv=None):
                    help="--ppo-clip: use the advantages as they are, not normalised over the rollout")
     p.add_argument("--optimizer", default=None, choices=("adam", "rmsprop"),
                    help="the optimiser of the update (default rmsprop, the reference's)")
+    p.add_argument("--ppo-target-kl", type=float, default=None, metavar="KL",
+                   help="--ppo-clip: stop an update's optimiser steps once the approximate KL from the rollout's "
+                        "policy exceeds 1.5 KL, decided on the device (default: every step runs)")
+    p.add_argument("--ppo-kl-host-stop", action="store_true",
+                   help="--ppo-target-kl: read the stop on the host after every check and skip the remaining epochs "
+                        "(same result, saves their time; not with --cuda-graph)")
     a = p.parse_args(argv)
+    if a.ppo_target_kl is not None and a.ppo_clip is None:
+        p.error("--ppo-target-kl needs --ppo-clip")
+    if a.ppo_target_kl is not None and not a.ppo_target_kl > 0:
+        p.error("--ppo-target-kl must be > 0")
+    if a.ppo_kl_host_stop and a.ppo_target_kl is None:
+        p.error("--ppo-kl-host-stop needs --ppo-target-kl")
+    if a.ppo_kl_host_stop and a.cuda_graph:
+        p.error("--ppo-kl-host-stop and --cuda-graph exclude each other")
     if a.ppo_clip is None and (a.ppo_epochs is not None or a.ppo_value_clip is not None or a.no_adv_norm or
                                a.ppo_minibatches is not None):
         p.error("--ppo-epochs / --ppo-minibatches / --ppo-value-clip / --no-adv-norm need --ppo-clip")
@@ -683,9 +701,12 @@ def main(argv=None):
     if a.visit_counts:
         over["visit_counts"] = True
     for key, v in (("ppo_clip", a.ppo_clip), ("ppo_epochs", a.ppo_epochs), ("ppo_value_clip", a.ppo_value_clip),
-                   ("ppo_minibatches", a.ppo_minibatches), ("optimizer", a.optimizer)):
+                   ("ppo_minibatches", a.ppo_minibatches), ("optimizer", a.optimizer),
+                   ("ppo_target_kl", a.ppo_target_kl)):
         if v is not None:
             over[key] = v
+    if a.ppo_kl_host_stop:
+        over["ppo_kl_host_stop"] = True
     if a.no_adv_norm:
         over["ppo_normalize_advantage"] = False
     exp = make_trainer(a.name, env_kwargs=env_kwargs, save_dir=a.save_dir, seed=a.seed, **over)

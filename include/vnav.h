@@ -1093,6 +1093,32 @@ int vn_adam_step_dev(float* params, const float* grads, float* exp_avg, float* e
                      const float* scalars2, const float* lr_dev, int64_t* step_dev, float beta1, float beta2,
                      float eps, vn_stream_t stream);
 
+/* PPO target KL (DESIGN.md "PPO target KL", csrc/vn_ppo_kl.hip): the early stop of an update's
+ * epochs, decided and applied on the device so that the update stays one captured hipGraph.
+ *
+ * vn_ppo_kl_gate: gate_dev [2] int32 = [stopped, steps_allowed], kl_dev [2] f32 = [the KL of the
+ * last check, the KL that stopped the update]. With gate_dev[0] != 0 on entry the launch writes
+ * nothing (the stop is sticky until the caller zeroes the buffers). Otherwise
+ *   kl = (1 / n) sum_i (expm1f(d_i) - d_i), d_i = logp_a - logp_old_a as vn_ppo_loss_grad forms it
+ * (the k3 estimate behind ppo_stats4[0]), summed as vn_ppo_adv_stats sums: one launch of one
+ * workgroup, fp64 sums in a fixed order, the mean rounded once to fp32, no atomics, so the same
+ * input gives the same bits. kl_dev[0] = kl; then kl > kl_limit (strict) sets gate_dev[0] = 1 and
+ * kl_dev[1] = kl, else gate_dev[1] += 1. out and out_old may be one buffer (kl is then exactly 0).
+ * VN_EINVAL, nothing written: a NULL buffer, n <= 0, num_actions outside 1..7, kl_limit negative
+ * or NaN. */
+int vn_ppo_kl_gate(const float* out, const float* out_old, const int32_t* actions, int n, int num_actions,
+                   float kl_limit, int32_t* gate_dev, float* kl_dev, vn_stream_t stream);
+/* vn_adam_step_dev / vn_rmsprop_step_dev behind a flag read on the device: with *skip_dev == 0 the
+ * same expressions and the same bits; with *skip_dev != 0 nothing is written, not the parameters,
+ * not the moments or square_avg, and not Adam's step_dev (its advance launch reads the flag too).
+ * VN_EINVAL, nothing written: a NULL buffer (skip_dev included), n <= 0. */
+int vn_adam_step_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float scale,
+                       const float* scalars2, const float* lr_dev, int64_t* step_dev, float beta1, float beta2,
+                       float eps, const int32_t* skip_dev, vn_stream_t stream);
+int vn_rmsprop_step_gated(float* params, const float* grads, float* square_avg, int64_t n, float scale,
+                          const float* scalars2, const float* lr_dev, float alpha, float eps, const int32_t* skip_dev,
+                          vn_stream_t stream);
+
 /* Copy the message of the calling thread's last error (NUL-terminated). */
 int vn_last_error(char* buf, size_t len);
 const char* vn_version(void);

@@ -26,9 +26,19 @@ vn_ppo_minibatch_gather on their own. learn: PPO K = 4 with Adam at every M give
 <out>/ppo_minibatch_bench.json or <out>/ppo_minibatch_learn.json (default <out>:
 profiles/ppo_minibatch).
 
+--target-kl KL [KL ...] (DESIGN.md "PPO target KL"): the same two modes on the target-KL stop.
+cost: PPO K = 4 at M = 1 and 4 without the argument (the parent commit's update, bit for bit) and
+with ppo_target_kl at every KL given (give one that never fires, as 1e30, for the cost of the gate
+itself), at both points, variants alternating as above; and, at 4096 envs M = 1, a target of 1e-30,
+which fires at epoch 1's check, in the gated form and with ppo_kl_host_stop: what leaving the loops
+saves. learn: PPO K = 4, M = 4 with RMSprop and with Adam, without a target and at every KL given;
+beside the success rate the last update's clip_fraction and the mean ppo_steps over the run. Writes
+<out>/ppo_kl_bench.json or <out>/ppo_kl_learn.json (default <out>: profiles/ppo_kl).
+
 Writes <out>/ppo_bench.json or <out>/ppo_learn.json and prints the same JSON line.
 
-    python tools/ppo_bench.py [--mode cost|learn] [--minibatches M [M ...]] [--rounds 5] [--out DIR]
+    python tools/ppo_bench.py [--mode cost|learn] [--minibatches M [M ...]] [--target-kl KL [KL ...]]
+                              [--rounds 5] [--out DIR]
 """
 import argparse
 import json
@@ -162,7 +172,55 @@ def cost_minibatches(a, dev):
     return res, "ppo_minibatch_bench.json"
 
 
+def cost_target_kl(a, dev):
+    import vnav
+    K, Ms = 4, (1, 4)
+    res = {"tool": "ppo_bench", "mode": "cost", "target_kl": a.target_kl,
+           "config": {"seed": SEED, "rounds": a.rounds, "updates": a.updates, "update_warmup": a.update_warmup,
+                      "epochs": K, "minibatches": list(Ms), "stop_target": 1e-30},
+           "update": {"unit": "ms per A2CTrainer.step() (device, one event pair)"}}
+    points = (("envs4096_84_lstm", [vnav.synthetic_scene(k) for k in range(20)], 4096, False, 1),
+              ("envs4_174_graph", [vnav.synthetic_scene(0, frame_shape=(174, 174, 3))], 4, True, 10))
+    for name, sc, E, graph, mult in points:
+        variants = {}
+        for M in Ms:
+            base = dict(ppo_clip=0.2, ppo_epochs=K, ppo_minibatches=M)
+            variants["k4_m%d" % M] = base
+            for kl in a.target_kl:
+                variants["k4_m%d_kl%g" % (M, kl)] = dict(base, ppo_target_kl=kl)
+        if not graph:  # the stop at epoch 1 of 4: every launch still run, against leaving the loops
+            stop = dict(ppo_clip=0.2, ppo_epochs=K, ppo_target_kl=1e-30)
+            variants["k4_m1_stop_gated"] = stop
+            variants["k4_m1_stop_host"] = dict(stop, ppo_kl_host_stop=True)
+        ms = {v: [] for v in variants}
+        for r in range(a.rounds):
+            for v, kw in variants.items():
+                ms[v].append(time_update(kw, sc, E, graph, a.update_warmup, a.updates * mult, dev))
+                print("%s round %d %s: %.3f ms" % (name, r, v, ms[v][-1]), file=sys.stderr, flush=True)
+        sp = {v: spread(ms[v]) for v in variants}
+        med = {v: sp[v]["median"] for v in variants}
+        derived = {}
+        for M in Ms:
+            off = "k4_m%d" % M
+            for kl in a.target_kl:
+                on = "k4_m%d_kl%g" % (M, kl)
+                derived[on] = {"gate_cost_ms": med[on] - med[off],
+                               "by_round": [x - y for x, y in zip(ms[on], ms[off])],
+                               "off_spread_ms": sp[off]["max"] - sp[off]["min"]}
+        if not graph:
+            derived["host_stop_saves_ms"] = {"median": med["k4_m1_stop_gated"] - med["k4_m1_stop_host"],
+                                             "by_round": [x - y for x, y in zip(ms["k4_m1_stop_gated"],
+                                                                                ms["k4_m1_stop_host"])],
+                                             "per_skipped_epoch_ms":
+                                                 (med["k4_m1_stop_gated"] - med["k4_m1_stop_host"]) / (K - 1)}
+        res["update"][name] = dict(sp, envs=E, frame=list(sc[0].frame_shape), cuda_graph=graph,
+                                   updates_timed=a.updates * mult, derived=derived)
+    return res, "ppo_kl_bench.json"
+
+
 def cost(a, dev):
+    if a.target_kl:
+        return cost_target_kl(a, dev)
     if a.minibatches:
         return cost_minibatches(a, dev)
     import vnav
@@ -204,15 +262,18 @@ def learn_run(kw, seed, updates, dev):
     tr = vnav.A2CTrainer(env, num_steps=20, seed=seed, max_time_steps=1e6, nav_metrics=True, **kw)
     ok = eps = 0.0
     kl = clipped = None  # A2C reports neither
+    steps = []  # ppo_steps of every update (with ppo_target_kl)
     for u in range(updates):
         m = tr.step()
+        if "ppo_steps" in m:
+            steps.append(m["ppo_steps"])
         n_ep, n_ok = (float(x) for x in tr.nav_stats[:2].cpu())
         if u >= updates - 20:
             eps += n_ep
             ok += n_ok
         kl, clipped = m.get("approx_kl", kl), m.get("clip_fraction", clipped)
     env.close()
-    return ok / eps if eps else float("nan"), eps, kl, clipped
+    return ok / eps if eps else float("nan"), eps, kl, clipped, float(np.mean(steps)) if steps else None
 
 
 def learn(a, dev):
@@ -221,6 +282,14 @@ def learn(a, dev):
         variants = {"ppo4_adam_m%d" % M: dict(ppo_clip=0.2, ppo_epochs=4, optimizer="adam", ppo_minibatches=M)
                     for M in a.minibatches}
         name = "ppo_minibatch_learn.json"
+    if a.target_kl:
+        variants = {}
+        for opt in ("rmsprop", "adam"):
+            base = dict(ppo_clip=0.2, ppo_epochs=4, ppo_minibatches=4, optimizer=opt)
+            variants["ppo4_m4_%s" % opt] = base
+            for t in a.target_kl:
+                variants["ppo4_m4_%s_kl%g" % (opt, t)] = dict(base, ppo_target_kl=t)
+        name = "ppo_kl_learn.json"
     res = {"tool": "ppo_bench", "mode": "learn",
            "config": {"task": "synthetic_scene(0, grid=6), goal 7, limit 30", "envs": 16, "num_steps": 20,
                       "updates": a.learn_updates, "seeds": [0, 1, 2], "variants": variants,
@@ -229,8 +298,11 @@ def learn(a, dev):
            "runs": {}}
     for v, kw in variants.items():
         rows = [learn_run(kw, seed, a.learn_updates, dev) for seed in (0, 1, 2)]
+        print("%s: success %s" % (v, ["%.3f" % r[0] for r in rows]), file=sys.stderr, flush=True)
         res["runs"][v] = {"success_rate": [r[0] for r in rows], "episodes": [r[1] for r in rows],
                              "approx_kl": [r[2] for r in rows], "clip_fraction": [r[3] for r in rows]}
+        if a.target_kl:
+            res["runs"][v]["ppo_steps_mean"] = [r[4] for r in rows]
     return res, name
 
 
@@ -243,12 +315,17 @@ def main():
     ap.add_argument("--learn-updates", type=int, default=120)
     ap.add_argument("--minibatches", type=int, nargs="+", default=None, metavar="M",
                     help="measure the minibatch split at these M (writes ppo_minibatch_*.json)")
+    ap.add_argument("--target-kl", type=float, nargs="+", default=None, metavar="KL",
+                    help="measure the target-KL stop at these targets (writes ppo_kl_*.json)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.target_kl and not min(a.target_kl) > 0:
+        ap.error("--target-kl must be > 0")
     if a.minibatches and min(a.minibatches) < 1:
         ap.error("--minibatches must be at least 1")
     if a.out is None:
-        a.out = os.path.join(REPO, "profiles", "ppo_minibatch" if a.minibatches else "ppo")
+        sub = "ppo_kl" if a.target_kl else "ppo_minibatch" if a.minibatches else "ppo"
+        a.out = os.path.join(REPO, "profiles", sub)
     if not torch.cuda.is_available():
         raise SystemExit("ppo_bench needs the GPU (no CPU timing)")
     dev = torch.device("cuda", 0)
