@@ -342,6 +342,9 @@ class A2CTrainer:
                                             ppo=self.ppo,  # step()'s vector: {segment: (offset, width)}
                                             ppo_kl=self.ppo_target_kl is not None)
         self.workspace = torch.empty(self.net.workspace_floats(N), dtype=torch.float32, **kw)
+        # what _forward_stored / _backward read beside the frames: the LSTM inputs and start state
+        # (recurrent), and the aux heads' targets; the minibatches have their own (self.mb)
+        self._seq, self._aux_targets = {}, None
         if self.recurrent:
             X = self.net.lstm["xcat"]
             A1 = self.A + 1
@@ -359,6 +362,7 @@ class A2CTrainer:
             if self.ppo:  # the rollout's last (h, c), saved before an epoch's re-forward overwrites them
                 self._hc_last = torch.zeros((2, E, 512), **f32)
             self.h0, self.c0 = self._hc0[0], self._hc0[1]
+            self._seq = dict(lra=self.lra, masks=self.masks, h0=self.h0, c0=self.c0)
             self.prev_action = torch.zeros(E, dtype=torch.int64, **kw)
             self.prev_reward = torch.zeros(E, **f32)
             self.prev_mask = torch.zeros(E, **f32)    # 0: the first step starts every episode
@@ -546,6 +550,7 @@ class A2CTrainer:
         self._mb_src = _lib.PpoRollout(**{k: v.data_ptr() for k, v in src.items()})
         self._mb_dst = _lib.PpoRollout(**{k: v.data_ptr() for k, v in mb.items()})
         self._mb_frames = self._frames(mb["rows_img"], mb["rows_goal"])
+        self._mb_aux_targets = None
         if self.aux_weight > 0:
             self._mb_aux_targets = AuxTargets(self.aux_table.data_ptr(), mb["rows_img"].data_ptr(),
                                               mb["rows_goal"].data_ptr())
@@ -789,6 +794,11 @@ class A2CTrainer:
         env.visit_stats(out=self.visit_seen)
         return self.rewards_aug
 
+    def _return_rewards(self):
+        """The rewards the update's returns are formed from: the env's own, or with a novelty
+        bonus rewards_aug (one launch, _novelty_rewards)."""
+        return self._novelty_rewards() if self.novelty else self.rewards
+
     def shaping_weight_at(self, steps):
         """The annealed shaping weight at an env-step count, as the device forms it: fp64, rounded
         once to fp32."""
@@ -890,12 +900,8 @@ class A2CTrainer:
         x5 = net.x5(self.ur_acts, cap)  # the LSTM and the heads run on the slot's n rows only
         h_r, c_r = self.ur_hc[0], self.ur_hc[1]
         h0, c0 = u["hc0"][0], u["hc0"][1]
-        for t in range(T + 1):
-            sl = slice(t * S, (t + 1) * S)
-            hp = h0 if t == 0 else h_r[(t - 1) * S:t * S]
-            cp = c0 if t == 0 else c_r[(t - 1) * S:t * S]
-            net.lstm_step(self.params, S, x5[sl], u["lra"][t], u["masks"][t], hp, cp, self.ur_xcat[sl],
-                          self.ur_gates, self.ur_lacts[sl], c_r[sl], h_r[sl])
+        net.lstm_sequence(self.params, T + 1, S, x5, u["lra"], u["masks"], h0, c0, self.ur_xcat, self.ur_gates,
+                          self.ur_lacts, c_r, h_r)
         net.heads(self.params, h_r, n, self.ur_out)
         self.ur_dout.zero_()
         rew, don = u["rewards"], u["dones"]
@@ -1148,8 +1154,7 @@ class A2CTrainer:
                 with torch.cuda.stream(self._side_u):
                     self._unreal_replay_losses()
                     self._ev_u1.record(self._side_u)
-        self._returns(self._novelty_rewards() if self.novelty else self.rewards, self.dones, self.boot_out, self.out,
-                      T, E, self.returns)
+        self._returns(self._return_rewards(), self.dones, self.boot_out, self.out, T, E, self.returns)
         if self.expert:  # the same launch shape, with the expert term: the update gains no launch
             _lib.check(lib.vn_a2c_loss_grad_expert(
                 _lib.ptr(self.out), _lib.ptr(self.actions), _lib.ptr(self.returns), _lib.ptr(self.expert_mask), N, A,
@@ -1181,10 +1186,7 @@ class A2CTrainer:
             # (in line: a side stream measured slower — their persistent kernels size their grids
             # to the whole chip, so nothing runs beside them; DESIGN "Two streams in the update")
             self.aux_stats.zero_()
-            net.aux_forward_loss_grad(self.params, self.acts, N, N, self.a1, self.pred, self._aux_targets,
-                                      self.aux_weight, self.dpred, self.aux_stats, self.aux_ws)
-            net.aux_backward(self.params, self.acts, N, N, self.a1, self.dpred, self.grads, self.dx4, self.aux_ws)
-            dx4 = self.dx4
+            dx4 = self._aux_heads_backward(N, self._aux_targets)
         if self.unreal and self.unreal_source == "rollout":  # after the aux heads: rp adds to their dX4
             S = self.unreal_S
             dx4 = self.dx4 if self.rp_into_aux else self.unreal_dx4
@@ -1192,27 +1194,11 @@ class A2CTrainer:
                                      self.actions, self.rewards, self.dones, self.rows_img, self.env._info["img_row"],
                                      T, E, S, dx4, self.rp_into_aux, h_src=(self.h_all, self.boot_h))
             unreal_dh = self.dh_pc[:T * S]
-        frames = self._frames(self.rows_img, self.rows_goal)
-        goals = None
-        if self.dedup_goals:  # the rollout's goal runs: starts ascending, run lengths
-            P = _lib.ptr
-            _lib.check(lib.vn_goal_runs_rollout(P(self.dones), T, E, P(self.goal_list), P(self.goal_run_length),
-                                                P(self.goal_count[T:T + 1]), st), "vn_goal_runs_rollout")
-            goals = self._goal_runs_update
-        if self.recurrent:
-            net.lstm_backward(self.params, T, E, self.dout, self.h_all, self.xcat, self.lstm_acts, self.c_all, self.c0,
-                              self.masks, net.x5(self.acts, N), self.dz5, self.grads, self.lstm_ws,
-                              dh_extra=unreal_dh, extra_envs=self.unreal_S if self.unreal else 0)
-            # the heads + LSTM (+ aux heads) gradients are final here: their all-reduce runs on
-            # RCCL's stream while the trunk backward runs on this one
-            self._allreduce_head_bucket()
-            net.backward_ex(self.params, frames, N, self.acts, N, None, self.dz5, dx4, self.grads, self.workspace,
-                            goals=goals)
-            # (h, c) after the last step carry into the next rollout (one copy launch)
+        goals = self._rollout_goal_runs(self.dones, T, E)
+        self._backward(E, self._frames(self.rows_img, self.rows_goal), self._seq, goals, dx4, dh_extra=unreal_dh,
+                       extra_envs=self.unreal_S if self.unreal else 0)
+        if self.recurrent:  # (h, c) after the last step carry into the next rollout (one copy launch)
             self._carry_states()
-        else:
-            net.backward_ex(self.params, frames, N, self.acts, N, self.dout, None, dx4, self.grads, self.workspace,
-                            goals=goals)
         # the side passes' gradient sums: in the norm's first pass (vn_grad_norm_join) on one
         # rank with no override; before the all-reduce / the override's autograd otherwise
         joins = []
@@ -1236,34 +1222,98 @@ class A2CTrainer:
                 if g is not None:
                     self.grads.add_(g)
         scale = self._allreduce_tail()
-        P = net.n_params
-        if joins:
-            (a0, lo0, hi0), (a1, lo1, hi1) = (joins + [(None, 0, 0)])[:2]
-            _lib.check(lib.vn_grad_norm_join(_lib.ptr(self.grads), P, _lib.ptr(a0), lo0, hi0, _lib.ptr(a1), lo1, hi1,
-                                             ctypes.c_float(scale), ctypes.c_float(self.max_gradient_norm),
-                                             _lib.ptr(self.norm_partial), _lib.ptr(self.scalars), st),
-                       "vn_grad_norm_join")
-        else:
-            _lib.check(lib.vn_grad_norm(_lib.ptr(self.grads), P, ctypes.c_float(scale),
-                                        ctypes.c_float(self.max_gradient_norm), _lib.ptr(self.norm_partial),
-                                        _lib.ptr(self.scalars), st), "vn_grad_norm")
-        if self.optimizer == "adam":
-            return self._adam_step(scale)
-        # lr of this update from the device schedule (== current_lr() of the host counters)
-        _lib.check(lib.vn_rmsprop_step_dev(_lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.square_avg), P,
-                                           ctypes.c_float(scale), _lib.ptr(self.scalars), _lib.ptr(self.lr_dev),
-                                           ctypes.c_float(self.rms_alpha), ctypes.c_float(self.rms_epsilon), st),
-                   "vn_rmsprop_step_dev")
+        if not joins:
+            return self._optimizer_step(scale, False)
+        (a0, lo0, hi0), (a1, lo1, hi1) = (joins + [(None, 0, 0)])[:2]
+        _lib.check(lib.vn_grad_norm_join(_lib.ptr(self.grads), net.n_params, _lib.ptr(a0), lo0, hi0, _lib.ptr(a1), lo1,
+                                         hi1, ctypes.c_float(scale), ctypes.c_float(self.max_gradient_norm),
+                                         _lib.ptr(self.norm_partial), _lib.ptr(self.scalars), st), "vn_grad_norm_join")
+        self._clipped_step(scale, False)
 
-    def _adam_step(self, scale):
-        """torch's Adam on the clipped gradient, lr from the device schedule and the step count from
-        the device (vn_adam_step_dev): nothing of the host enters, so a captured update stays valid."""
+    def _rollout_goal_runs(self, dones, T, E):
+        """The goal runs of a stored [T, E] rollout (run starts ascending, run lengths) from its
+        ``dones``: one vn_goal_runs_rollout launch into the update's lists. Returns the GoalRuns
+        for the policy's calls over its T * E rows; None, and no launch, where those take none."""
+        if not self.dedup_goals:
+            return None
+        goals = self._goal_runs_update if E == self.env.num_envs else self._mb_goal_runs.get(E)
+        if goals is not None:
+            P = _lib.ptr
+            _lib.check(self.lib.vn_goal_runs_rollout(P(dones), T, E, P(self.goal_list), P(self.goal_run_length),
+                                                     P(self.goal_count[T:T + 1]), self._stream()),
+                       "vn_goal_runs_rollout")
+        return goals
+
+    def _forward_stored(self, E, frames, seq, goals):
+        """The stored rollout, or E of its envs, under the current parameters, into the rollout's
+        own activation buffers and self.out: one trunk call over the T * E rows of ``frames``;
+        recurrent, the T LSTM steps from seq's (h0, c0) over its stored lra and masks
+        (lstm_sequence), then the heads. The activation store keeps its capacity of N rows."""
+        net, T = self.net, self.num_steps
+        n, N = T * E, T * self.env.num_envs
+        if not self.recurrent:
+            net.forward(self.params, frames, n, self.acts, N, 0, self.out, goals=goals)
+            return
+        net.forward(self.params, frames, n, self.acts, N, 0, None, goals=goals)
+        net.lstm_sequence(self.params, T, E, net.x5(self.acts, N), seq["lra"], seq["masks"], seq["h0"], seq["c0"],
+                          self.xcat, self.gates, self.lstm_acts, self.c_all, self.h_all)
+        net.heads(self.params, self.h_all, n, self.out)
+
+    def _aux_heads_backward(self, n, targets):
+        """The deconv heads on the first n rows of the rollout's activations: forward with the loss
+        gradient against ``targets`` (sums added to aux_stats), backward into their gradient
+        blocks and self.dx4. Returns dx4; None, and no launch, without targets."""
+        if targets is None:
+            return None
+        net, N = self.net, self.num_steps * self.env.num_envs
+        net.aux_forward_loss_grad(self.params, self.acts, N, n, self.a1, self.pred, targets, self.aux_weight,
+                                  self.dpred, self.aux_stats, self.aux_ws)
+        net.aux_backward(self.params, self.acts, N, n, self.a1, self.dpred, self.grads, self.dx4, self.aux_ws)
+        return self.dx4
+
+    def _backward(self, E, frames, seq, goals, dx4, dh_extra=None, extra_envs=0):
+        """self.dout and ``dx4`` (the heads' dL/dX4, None without) back through the T * E rows of
+        ``frames`` in the rollout's activation buffers, into grads: recurrent, the LSTM backward
+        from seq's c0 under its masks (``dh_extra``: pixel control's dL/dh of the first
+        ``extra_envs`` envs) and the trunk backward of dz5; else the heads and trunk backward of dout."""
+        net, T = self.net, self.num_steps
+        n, N = T * E, T * self.env.num_envs
+        if not self.recurrent:
+            net.backward_ex(self.params, frames, n, self.acts, N, self.dout, None, dx4, self.grads, self.workspace,
+                            goals=goals)
+            return
+        net.lstm_backward(self.params, T, E, self.dout, self.h_all, self.xcat, self.lstm_acts, self.c_all,
+                          seq["c0"], seq["masks"], net.x5(self.acts, N), self.dz5, self.grads, self.lstm_ws,
+                          dh_extra=dh_extra, extra_envs=extra_envs)
+        # the heads + LSTM (+ aux heads) gradients are final here: at world > 1 their all-reduce
+        # runs on RCCL's stream while the trunk backward runs on this one (no launch at world 1)
+        self._allreduce_head_bucket()
+        net.backward_ex(self.params, frames, n, self.acts, N, None, self.dz5, dx4, self.grads, self.workspace,
+                        goals=goals)
+
+    def _clipped_step(self, scale, gated):
+        """One RMSprop or Adam step on the gradient the norm launch has measured (scalars: the clip
+        factor), lr from the device schedule (== current_lr() of the host counters) and Adam's step
+        count from the device: nothing of the host enters, so a captured update stays valid.
+        ``gated``: the entry point that reads ppo_target_kl's stop flag and writes nothing once set."""
         P, c_float = _lib.ptr, ctypes.c_float
-        _lib.check(self.lib.vn_adam_step_dev(P(self.params), P(self.grads), P(self.exp_avg), P(self.exp_avg_sq),
-                                             self.net.n_params, c_float(scale), P(self.scalars), P(self.lr_dev),
-                                             P(self.adam_step), c_float(self.adam_betas[0]),
-                                             c_float(self.adam_betas[1]), c_float(self.adam_epsilon), self._stream()),
-                   "vn_adam_step_dev")
+        name = "vn_%s_step_%s" % (self.optimizer, "gated" if gated else "dev")
+        if self.optimizer == "adam":
+            state = (P(self.exp_avg), P(self.exp_avg_sq))
+            hyper = (P(self.adam_step), c_float(self.adam_betas[0]), c_float(self.adam_betas[1]),
+                     c_float(self.adam_epsilon))
+        else:
+            state, hyper = (P(self.square_avg),), (c_float(self.rms_alpha), c_float(self.rms_epsilon))
+        gate = (P(self.kl_gate),) if gated else ()
+        _lib.check(getattr(self.lib, name)(P(self.params), P(self.grads), *state, self.net.n_params, c_float(scale),
+                                           P(self.scalars), P(self.lr_dev), *hyper, *gate, self._stream()), name)
+
+    def _optimizer_step(self, scale, gated):
+        """The norm of the gradient just formed (times ``scale``, 1 / world) and one clipped step."""
+        _lib.check(self.lib.vn_grad_norm(_lib.ptr(self.grads), self.net.n_params, ctypes.c_float(scale),
+                                         ctypes.c_float(self.max_gradient_norm), _lib.ptr(self.norm_partial),
+                                         _lib.ptr(self.scalars), self._stream()), "vn_grad_norm")
+        self._clipped_step(scale, gated)
 
     @property
     def on_ppo_epoch(self):
@@ -1291,46 +1341,25 @@ class A2CTrainer:
                              "cannot replay: use cuda_graph=False")
         self._on_ppo_minibatch = fn
 
-    def _ppo_reforward(self, goals):
-        """The stored rollout under the current parameters, into the rollout's own activation
-        buffers and self.out: one trunk call over all N rows, recurrent the T LSTM steps from the
-        (h0, c0) the rollout started from with its stored inputs and masks, then the heads."""
-        net, E, T = self.net, self.env.num_envs, self.num_steps
-        N = T * E
-        frames = self._frames(self.rows_img, self.rows_goal)
-        if not self.recurrent:
-            net.forward(self.params, frames, N, self.acts, N, 0, self.out, goals=goals)
-            return
-        net.forward(self.params, frames, N, self.acts, N, 0, None, goals=goals)
-        x5 = net.x5(self.acts, N)
-        for t in range(T):
-            sl = slice(t * E, (t + 1) * E)
-            hp = self.h0 if t == 0 else self.h_all[(t - 1) * E:t * E]
-            cp = self.c0 if t == 0 else self.c_all[(t - 1) * E:t * E]
-            net.lstm_step(self.params, E, x5[sl], self.lra[t], self.masks[t], hp, cp, self.xcat[sl], self.gates,
-                          self.lstm_acts[sl], self.c_all[sl], self.h_all[sl])
-        net.heads(self.params, self.h_all, N, self.out)
-
     def _ppo_update(self):
         """ppo_epochs full-batch epochs of the clipped surrogate on the rollout just sampled
         (DESIGN.md "PPO epochs"). The returns, the behaviour policy's head outputs (out_old) and
         the advantage statistics are formed once and stay fixed. Epoch 0 runs on the rollout's own
         stored activations, as the A2C update does; every later epoch first re-forwards the stored
-        rollout under the current parameters (the backward consumes activations). After the
-        loss-gradient launch each epoch is the A2C chain: aux heads, LSTM and trunk backward,
-        norm, optimiser step. The carried (h, c) is the behaviour policy's: saved before the first
-        re-forward, written into (h0, c0) after the last epoch, so c0 is the rollout's start state
-        for every epoch's LSTM backward. No host value enters: the K epochs are captured in the
-        update's one hipGraph. With ppo_minibatches > 1 the epochs are _ppo_minibatch_epochs'; what
-        is formed once here and the carry are the same. With ppo_target_kl every optimiser step has
-        the KL check in front of it (_ppo_kl_gate, DESIGN.md "PPO target KL"): its buffers are zeroed
-        here, and once it has fired the remaining epochs run their launches and change nothing."""
-        lib, net, P, c_float = self.lib, self.net, _lib.ptr, ctypes.c_float
+        rollout under the current parameters (_forward_stored: the backward consumes activations).
+        After the loss-gradient launch each epoch is the A2C update's own chain (_aux_heads_backward,
+        _backward, _optimizer_step). The carried (h, c) is the behaviour policy's: saved before the
+        first re-forward, written into (h0, c0) after the last epoch, so c0 is the rollout's start
+        state for every epoch's LSTM backward. No host value enters: the K epochs are captured in
+        the update's one hipGraph. With ppo_minibatches > 1 the epochs are _ppo_minibatch_epochs';
+        what is formed once here and the carry are the same. With ppo_target_kl every optimiser step
+        has the KL check in front of it (_ppo_kl_gate, DESIGN.md "PPO target KL"): its buffers are
+        zeroed here, and once it has fired the remaining epochs run their launches and change nothing."""
+        lib, P, c_float = self.lib, _lib.ptr, ctypes.c_float
         E, T, A = self.env.num_envs, self.num_steps, self.A
         N = T * E
         st = self._stream()
-        self._returns(self._novelty_rewards() if self.novelty else self.rewards, self.dones, self.boot_out, self.out,
-                      T, E, self.returns)
+        self._returns(self._return_rewards(), self.dones, self.boot_out, self.out, T, E, self.returns)
         self.out_old.copy_(self.out)
         if self.ppo_normalize_advantage:
             _lib.check(lib.vn_ppo_adv_stats(P(self.returns), P(self.out_old), N, A, c_float(_PPO_ADV_EPS), P(self.adv_stats),
@@ -1346,14 +1375,12 @@ class A2CTrainer:
                 self._hc0.copy_(self._hc_last)
             return
         frames = self._frames(self.rows_img, self.rows_goal)
-        goals = None
-        if self.dedup_goals:  # the rollout's goal runs, for every epoch's re-forward and backward alike
-            _lib.check(lib.vn_goal_runs_rollout(P(self.dones), T, E, P(self.goal_list), P(self.goal_run_length),
-                                                P(self.goal_count[T:T + 1]), st), "vn_goal_runs_rollout")
-            goals = self._goal_runs_update
+        # the rollout's goal runs, for every epoch's re-forward and backward alike
+        goals = self._rollout_goal_runs(self.dones, T, E)
+        gated = self.ppo_target_kl is not None
         for k in range(self.ppo_epochs):
             if k > 0:
-                self._ppo_reforward(goals)
+                self._forward_stored(E, frames, self._seq, goals)
             if self._ppo_kl_gate(self.out, self.out_old, self.actions, N):
                 break
             _lib.check(lib.vn_ppo_loss_grad(
@@ -1361,23 +1388,10 @@ class A2CTrainer:
                 P(self.adv_stats) if self.ppo_normalize_advantage else None, N, A, c_float(self.ppo_clip),
                 c_float(self.ppo_value_clip), c_float(self.value_coefficient), c_float(self.entropy_coefficient),
                 P(self.dout), P(self.stats), P(self.ppo_stats), st), "vn_ppo_loss_grad")
-            dx4 = None
             if self.aux_weight > 0:  # the deconv heads on the rollout batch, as the A2C update runs them
                 self.aux_stats.zero_()
-                net.aux_forward_loss_grad(self.params, self.acts, N, N, self.a1, self.pred, self._aux_targets,
-                                          self.aux_weight, self.dpred, self.aux_stats, self.aux_ws)
-                net.aux_backward(self.params, self.acts, N, N, self.a1, self.dpred, self.grads, self.dx4, self.aux_ws)
-                dx4 = self.dx4
-            if self.recurrent:
-                net.lstm_backward(self.params, T, E, self.dout, self.h_all, self.xcat, self.lstm_acts, self.c_all,
-                                  self.c0, self.masks, net.x5(self.acts, N), self.dz5, self.grads, self.lstm_ws,
-                                  dh_extra=None, extra_envs=0)
-                net.backward_ex(self.params, frames, N, self.acts, N, None, self.dz5, dx4, self.grads, self.workspace,
-                                goals=goals)
-            else:
-                net.backward_ex(self.params, frames, N, self.acts, N, self.dout, None, dx4, self.grads,
-                                self.workspace, goals=goals)
-            self._ppo_optimizer_step()
+            self._backward(E, frames, self._seq, goals, self._aux_heads_backward(N, self._aux_targets))
+            self._optimizer_step(1.0, gated)
             if self._on_ppo_epoch is not None:
                 self._on_ppo_epoch(k)
         if self.recurrent:
@@ -1396,49 +1410,23 @@ class A2CTrainer:
                                            P(self.kl_gate), P(self.kl_dev), self._stream()), "vn_ppo_kl_gate")
         return self.ppo_kl_host_stop and bool(self.kl_gate[0].item())  # a 4-byte copy and a sync
 
-    def _ppo_optimizer_step(self):
-        """The norm of the gradient just formed and one clipped optimiser step (world 1); with
-        ppo_target_kl the step that reads the stop flag on the device."""
-        lib, n, P, c_float, st = self.lib, self.net.n_params, _lib.ptr, ctypes.c_float, self._stream()
-        _lib.check(lib.vn_grad_norm(P(self.grads), n, c_float(1.0), c_float(self.max_gradient_norm),
-                                    P(self.norm_partial), P(self.scalars), st), "vn_grad_norm")
-        if self.ppo_target_kl is not None:
-            if self.optimizer == "adam":
-                _lib.check(lib.vn_adam_step_gated(P(self.params), P(self.grads), P(self.exp_avg), P(self.exp_avg_sq), n,
-                                                  c_float(1.0), P(self.scalars), P(self.lr_dev), P(self.adam_step),
-                                                  c_float(self.adam_betas[0]), c_float(self.adam_betas[1]),
-                                                  c_float(self.adam_epsilon), P(self.kl_gate), st),
-                           "vn_adam_step_gated")
-            else:
-                _lib.check(lib.vn_rmsprop_step_gated(P(self.params), P(self.grads), P(self.square_avg), n, c_float(1.0),
-                                                     P(self.scalars), P(self.lr_dev), c_float(self.rms_alpha),
-                                                     c_float(self.rms_epsilon), P(self.kl_gate), st),
-                           "vn_rmsprop_step_gated")
-            return
-        if self.optimizer == "adam":
-            self._adam_step(1.0)
-        else:
-            _lib.check(lib.vn_rmsprop_step_dev(P(self.params), P(self.grads), P(self.square_avg), n, c_float(1.0),
-                                               P(self.scalars), P(self.lr_dev), c_float(self.rms_alpha),
-                                               c_float(self.rms_epsilon), st), "vn_rmsprop_step_dev")
-
     def _ppo_minibatch_epochs(self):
         """The epochs of a PPO update in ppo_minibatches = M shuffled minibatches of whole envs
         (DESIGN.md "PPO minibatches"). Per epoch one permutation of the envs, keyed by the update's
         counter (sched[2], read on the device); per minibatch one gather of its [T, Eb] sub-rollout
-        into the compact buffers, then the epoch's chain at Eb envs in the rollout's own activation
-        buffers: re-forward from the gathered start states (epoch 0 too: the rollout's stored
-        activations are in the full-batch layout), loss gradient with the mean over the minibatch's
-        own samples and the rollout's advantage statistics, aux heads, LSTM and trunk backward,
-        norm, optimiser step. The sums behind the metrics are cleared when an epoch begins and
-        added to by its minibatches, so they end as the final epoch's over all N samples."""
-        lib, net, P, c_float = self.lib, self.net, _lib.ptr, ctypes.c_float
+        into the compact buffers (self.mb), then the full-batch epoch's chain at Eb envs in the
+        rollout's own activation buffers: _forward_stored from the gathered start states (epoch 0
+        too: the rollout's stored activations are in the full-batch layout), loss gradient with the
+        mean over the minibatch's own samples and the rollout's advantage statistics,
+        _aux_heads_backward, _backward, _optimizer_step. The sums behind the metrics are cleared
+        when an epoch begins and added to by its minibatches, so they end as the final epoch's over
+        all N samples."""
+        lib, P, c_float = self.lib, _lib.ptr, ctypes.c_float
         E, T, A, M = self.env.num_envs, self.num_steps, self.A, self.ppo_minibatches
-        N = T * E
         st = self._stream()
         mb, frames = self.mb, self._mb_frames
         counter = self.sched[2:3]
-        x5 = net.x5(self.acts, N) if self.recurrent else None
+        gated = self.ppo_target_kl is not None
         stopped = False  # ppo_kl_host_stop: the host has seen the stop flag set
         for k in range(self.ppo_epochs):
             _lib.check(lib.vn_ppo_env_permutation(self._ppo_seed, P(counter), k, E, 32, P(self.ppo_perm), st),
@@ -1453,22 +1441,8 @@ class A2CTrainer:
                 _lib.check(lib.vn_ppo_minibatch_gather(ctypes.byref(self._mb_src), ctypes.byref(self._mb_dst),
                                                        P(self.ppo_perm[lo:]), eb, T, E, A, st),
                            "vn_ppo_minibatch_gather")
-                goals = self._mb_goal_runs.get(eb)
-                if goals is not None:  # this minibatch's goal runs, from its gathered dones
-                    _lib.check(lib.vn_goal_runs_rollout(P(mb["dones"]), T, eb, P(self.goal_list),
-                                                        P(self.goal_run_length), P(self.goal_count[T:T + 1]), st),
-                               "vn_goal_runs_rollout")
-                if self.recurrent:
-                    net.forward(self.params, frames, nb, self.acts, N, 0, None, goals=goals)
-                    for t in range(T):
-                        sl = slice(t * eb, (t + 1) * eb)
-                        hp = mb["h0"] if t == 0 else self.h_all[(t - 1) * eb:t * eb]
-                        cp = mb["c0"] if t == 0 else self.c_all[(t - 1) * eb:t * eb]
-                        net.lstm_step(self.params, eb, x5[sl], mb["lra"][sl], mb["masks"][sl], hp, cp, self.xcat[sl],
-                                      self.gates, self.lstm_acts[sl], self.c_all[sl], self.h_all[sl])
-                    net.heads(self.params, self.h_all, nb, self.out)
-                else:
-                    net.forward(self.params, frames, nb, self.acts, N, 0, self.out, goals=goals)
+                goals = self._rollout_goal_runs(mb["dones"], T, eb)  # from its gathered dones
+                self._forward_stored(eb, frames, mb, goals)
                 # the KL over the minibatch's own samples against its gathered out_old
                 stopped = self._ppo_kl_gate(self.out, mb["out_old"], mb["actions"], nb)
                 if stopped:
@@ -1478,23 +1452,9 @@ class A2CTrainer:
                     P(self.adv_stats) if self.ppo_normalize_advantage else None, nb, A, c_float(self.ppo_clip),
                     c_float(self.ppo_value_clip), c_float(self.value_coefficient), c_float(self.entropy_coefficient),
                     P(self.dout), P(self.stats), P(self.ppo_stats), st), "vn_ppo_loss_grad_acc")
-                dx4 = None
-                if self.aux_weight > 0:  # the deconv heads on the minibatch: targets by its gathered rows
-                    net.aux_forward_loss_grad(self.params, self.acts, N, nb, self.a1, self.pred, self._mb_aux_targets,
-                                              self.aux_weight, self.dpred, self.aux_stats, self.aux_ws)
-                    net.aux_backward(self.params, self.acts, N, nb, self.a1, self.dpred, self.grads, self.dx4,
-                                     self.aux_ws)
-                    dx4 = self.dx4
-                if self.recurrent:
-                    net.lstm_backward(self.params, T, eb, self.dout, self.h_all, self.xcat, self.lstm_acts, self.c_all,
-                                      mb["c0"], mb["masks"], x5, self.dz5, self.grads, self.lstm_ws, dh_extra=None,
-                                      extra_envs=0)
-                    net.backward_ex(self.params, frames, nb, self.acts, N, None, self.dz5, dx4, self.grads,
-                                    self.workspace, goals=goals)
-                else:
-                    net.backward_ex(self.params, frames, nb, self.acts, N, self.dout, None, dx4, self.grads,
-                                    self.workspace, goals=goals)
-                self._ppo_optimizer_step()
+                # the deconv heads on the minibatch: targets by its gathered rows
+                self._backward(eb, frames, mb, goals, self._aux_heads_backward(nb, self._mb_aux_targets))
+                self._optimizer_step(1.0, gated)
                 if self._on_ppo_minibatch is not None:
                     self._on_ppo_minibatch(k, m)
             if stopped:  # left inside epoch k: it did not finish, its hook does not run

@@ -547,6 +547,19 @@ class PolicyNet:
                                                  P(c_prev), P(xcat), P(gates), P(acts), P(c_out), P(h_out),
                                                  _lib.stream_ptr(self.device)), "vn_lstm_forward_step")
 
+    def lstm_sequence(self, params, T, E, x5, lra, masks, h0, c0, xcat, gates, acts, c_all, h_all):
+        """T lstm_step calls from (h0, c0) over time-major buffers (step t = rows t*E .. (t+1)*E of
+        x5, xcat, acts, c_all and h_all): step t reads the (h, c) that step t - 1 wrote. lra and
+        masks are the flat time-major [T*E, A + 1] and [T*E] in any contiguous shape ([T, E, A + 1]);
+        gates is one [E, 2048] scratch."""
+        lra, masks = lra.view(-1, self.num_actions + 1), masks.view(-1)
+        hp, cp = h0, c0
+        for t in range(T):
+            sl = slice(t * E, (t + 1) * E)
+            self.lstm_step(params, E, x5[sl], lra[sl], masks[sl], hp, cp, xcat[sl], gates, acts[sl], c_all[sl],
+                           h_all[sl])
+            hp, cp = h_all[sl], c_all[sl]
+
     def heads(self, params, feat, n, out):
         _lib.check(self.lib.vn_policy_heads(self._h, _lib.ptr(params), _lib.ptr(feat), int(n), _lib.ptr(out),
                                             _lib.stream_ptr(self.device)), "vn_policy_heads")
@@ -626,6 +639,22 @@ class _GoalNavFunction(torch.autograd.Function):
         return grads, None, None, None
 
 
+def _recurrent_features(params, image, goal, lra, masks, h0, c0, net, T, B):
+    """The trunk over all T*B samples (time-major rows t*B + b) and the LSTM over their T steps from
+    (h0, c0), into fresh buffers: (acts, xcat, la, c_all, h_all), what the backward reads."""
+    n = T * B
+    f32 = dict(dtype=torch.float32, device=params.device)
+    acts = net.new_acts(n)
+    net.forward(params, frames_from_batch(image, goal), n, acts, n, 0, None)
+    xcat = torch.empty((n, net.lstm["xcat"]), **f32)
+    gates = torch.empty((B, 2048), **f32)
+    la = torch.empty((n, 2048), **f32)
+    c_all = torch.empty((n, 512), **f32)
+    h_all = torch.empty((n, 512), **f32)
+    net.lstm_sequence(params, T, B, net.x5(acts, n), lra, masks, h0, c0, xcat, gates, la, c_all, h_all)
+    return acts, xcat, la, c_all, h_all
+
+
 class _RecurrentGoalNavFunction(torch.autograd.Function):
     """Trunk over all T*B samples (time-major rows t*B + b), LSTM steps, heads on h.
     Gradients reach the parameters only: BPTT stops at the states entering the sequence
@@ -638,23 +667,8 @@ class _RecurrentGoalNavFunction(torch.autograd.Function):
         if image.shape[0] != n or lra.shape != (n, net.num_actions + 1) or masks.shape != (T, B) or \
                 h0.shape != (B, 512) or c0.shape != (B, 512):
             raise ValueError("recurrent inputs do not match T=%d, B=%d" % (T, B))
-        dev = params.device
-        acts = net.new_acts(n)
-        frames = frames_from_batch(image, goal)
-        net.forward(params, frames, n, acts, n, 0, None)
-        x5 = net.x5(acts, n)
-        L = net.lstm
-        xcat = torch.empty((n, L["xcat"]), dtype=torch.float32, device=dev)
-        gates = torch.empty((B, 2048), dtype=torch.float32, device=dev)
-        la = torch.empty((n, 2048), dtype=torch.float32, device=dev)
-        c_all = torch.empty((n, 512), dtype=torch.float32, device=dev)
-        h_all = torch.empty((n, 512), dtype=torch.float32, device=dev)
-        hp, cp = h0, c0
-        for t in range(T):
-            sl = slice(t * B, (t + 1) * B)
-            net.lstm_step(params, B, x5[sl], lra[sl], masks[t], hp, cp, xcat[sl], gates, la[sl], c_all[sl], h_all[sl])
-            hp, cp = h_all[sl], c_all[sl]
-        out = torch.empty((n, OUT_LD), dtype=torch.float32, device=dev)
+        acts, xcat, la, c_all, h_all = _recurrent_features(params, image, goal, lra, masks, h0, c0, net, T, B)
+        out = torch.empty((n, OUT_LD), dtype=torch.float32, device=params.device)
         net.heads(params, h_all, n, out)
         ctx.save_for_backward(params, image, goal, acts, xcat, la, c_all, h_all, c0, masks)
         ctx.net, ctx.T, ctx.B = net, T, B
@@ -723,23 +737,7 @@ class _RecurrentFeaturesFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, params, image, goal, lra, masks, h0, c0, net, T, B):
         net.check_frames(image, goal)
-        n = T * B
-        dev = params.device
-        acts = net.new_acts(n)
-        frames = frames_from_batch(image, goal)
-        net.forward(params, frames, n, acts, n, 0, None)
-        x5 = net.x5(acts, n)
-        L = net.lstm
-        xcat = torch.empty((n, L["xcat"]), dtype=torch.float32, device=dev)
-        gates = torch.empty((B, 2048), dtype=torch.float32, device=dev)
-        la = torch.empty((n, 2048), dtype=torch.float32, device=dev)
-        c_all = torch.empty((n, 512), dtype=torch.float32, device=dev)
-        h_all = torch.empty((n, 512), dtype=torch.float32, device=dev)
-        hp, cp = h0, c0
-        for t in range(T):
-            sl = slice(t * B, (t + 1) * B)
-            net.lstm_step(params, B, x5[sl], lra[sl], masks[t], hp, cp, xcat[sl], gates, la[sl], c_all[sl], h_all[sl])
-            hp, cp = h_all[sl], c_all[sl]
+        acts, xcat, la, c_all, h_all = _recurrent_features(params, image, goal, lra, masks, h0, c0, net, T, B)
         ctx.save_for_backward(params, image, goal, acts, xcat, la, c_all, h_all, c0, masks)
         ctx.net, ctx.T, ctx.B = net, T, B
         hT, cT = h_all[(T - 1) * B:].clone(), c_all[(T - 1) * B:].clone()
